@@ -60,6 +60,8 @@ def main():
     ap.add_argument("--settle-ms", type=float, default=30.0, help="how long the device is kept busy with the benchmarked step in front of the headline region")
     ap.add_argument("--settle-regions", type=int, default=0, help="experiment: untimed W + K regions (each closed by a sync) at the end of the settling phase")
     ap.add_argument("--no-settle", action="store_true", help="time the W + K steps as the first GPU work of the process only (no clock settling in front of the headline region)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the headline region, write what its last step computed (scores, mappings, a fixed sample of the verdict matrix) as DIR/<name>.npy")
     args = ap.parse_args()
 
     # stdout carries exactly one line: the result.  Native libraries are chatty on it (gloo's "[Gloo] Rank 0 is
@@ -149,6 +151,10 @@ def main():
             eng.sync()
             settled += args.warmup + args.steps
     dt = timed_region()
+    if args.dump_outputs:
+        last = eng.fetch(want_bitmap=True, want_map=True)      # (every rank: the fetch finishes the pipeline's all-reduces)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, *last)
     if dist is not None:
         import torch
         t = torch.tensor([dt], dtype=torch.float64)
@@ -248,6 +254,33 @@ def main():
         dist.barrier()
         eng.comm_destroy()
         dist.destroy_process_group()
+
+
+DUMP_BITMAP_BYTES = 32 << 20     # the verdict matrix's share of --dump-outputs (the whole dump stays under 64 MB)
+
+
+def dump_outputs(out_dir, score, bitmap, maps):
+    """What a caller of the timed path receives from its last step, as float arrays that hold every bit: the packed u64
+    scores and verdict words split into their 32-bit halves (float64 is exact on those), the mapping fields as float32.
+    The verdict matrix (chunks x pods, rank 0's node shard) is cut to a fixed, seeded sample of pod columns when the
+    whole of it would not fit the budget; `bitmap_pods` names the columns kept."""
+    os.makedirs(out_dir, exist_ok=True)
+
+    def halves(a):
+        a = np.asarray(a, np.uint64)
+        return (a >> np.uint64(32)).astype(np.float64), (a & np.uint64(0xFFFFFFFF)).astype(np.float64)
+
+    P = len(score)
+    keep = max(1, min(P, DUMP_BITMAP_BYTES // (16 * max(1, bitmap.shape[0]))))
+    cols = np.arange(P) if keep == P else np.sort(np.random.default_rng(20261015).choice(P, keep, replace=False))
+    arrays = {"bitmap_pods": cols.astype(np.float64)}
+    arrays["score_hi"], arrays["score_lo"] = halves(score)
+    arrays["bitmap_hi"], arrays["bitmap_lo"] = halves(bitmap[:, cols])
+    for f in maps.dtype.names:
+        if f != "pad":
+            arrays["map_" + f] = maps[f].astype(np.float32)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
 
 
 def settle(eng, now, settle_ms=30.0, min_steps=1000, fixed_steps=0):

@@ -37,3 +37,12 @@ def ref():
         pytest.skip("reference tree not present")
     r = ref_loader.load()
     return r
+
+
+@pytest.fixture
+def refans(request):
+    """The reference's answers for this test: live where the reference is present, stored ones elsewhere (tests/refanswers.py)."""
+    from tests import refanswers
+    a = refanswers.Answers(request.module.__name__, request.node.name)
+    yield a
+    a.finish()

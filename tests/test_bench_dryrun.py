@@ -173,3 +173,30 @@ def test_bench_four_ranks_strong_shape(tmp_path):
     out = json.loads([ln for ln in outs[0][0].splitlines() if ln.strip()][0])
     assert out["scaling"] == "strong" and out["n_gpus"] == 4 and out["config"]["nodes_total"] == 1200 and out["config"]["nodes_per_gpu"] == 300
     assert out["placed_pods"] > 0
+
+
+_DUMP_SCRIPT = _SINGLE_SCRIPT.replace('"--no-pmc"]', '"--no-pmc", "--no-extras", "--no-cpu-baseline", "--dump-outputs", sys.argv[1]]')
+
+
+def test_bench_dump_outputs(tmp_path):
+    """`--dump-outputs DIR`: the last timed step's scores, mappings and verdict words as float arrays (bit-exact), the same
+    from run to run with the same arguments."""
+    import subprocess
+    import numpy as np
+    script = tmp_path / "dump.py"
+    script.write_text(_DUMP_SCRIPT.format(root=ROOT, bench=os.path.join(ROOT, "bench.py")))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    dumps = []
+    for run in ("a", "b"):
+        res = subprocess.run([sys.executable, str(script), str(tmp_path / run)], env=env, capture_output=True, text=True, timeout=300)
+        assert res.returncode == 0, res.stderr
+        files = sorted(p.name for p in (tmp_path / run).iterdir())
+        dumps.append({f: np.load(tmp_path / run / f) for f in files})
+    a, b = dumps
+    assert set(a) >= {"score_hi.npy", "score_lo.npy", "bitmap_hi.npy", "bitmap_lo.npy", "bitmap_pods.npy", "map_gpu.npy", "map_cpu.npy", "map_valid.npy"}
+    assert set(a) == set(b) and all(np.array_equal(a[f], b[f]) for f in a)
+    assert all(x.dtype in (np.float32, np.float64) for x in a.values())
+    assert sum(x.nbytes for x in a.values()) <= 64 << 20
+    score = (a["score_hi.npy"].astype(np.uint64) << np.uint64(32)) | a["score_lo.npy"].astype(np.uint64)
+    assert score.shape == (96,) and np.count_nonzero(score) > 0 and np.count_nonzero(a["map_valid.npy"]) > 0
+    assert a["bitmap_hi.npy"].shape == (16, 96) and np.array_equal(a["bitmap_pods.npy"], np.arange(96))
