@@ -524,6 +524,36 @@ int nhdfit_set_outputs(nhdfit_ctx* ctx, int want_bitmap, int want_map);
 int nhdfit_get_stats(nhdfit_ctx* ctx, nhdfit_stats* out);
 int nhdfit_reset_stats(nhdfit_ctx* ctx);
 
+/* ---- explain: the stage at which each node turned each pod away -------------------------------------------------------
+ * The reference says why it dropped a node only in a log line per node (nhd/Matcher.py:72-358); these calls count, per pod,
+ * the nodes each stage dropped - every node is charged with the FIRST stage that drops it, in the reference's order.
+ * Stages 4..8 ask the fit path's own questions (nhd_amd/csrc/explain_core.h), so FITS is exactly the verdict bit of
+ * nhdfit_find / nhdfit_big_find for the pair.  A request the device cannot evaluate (invalid map type) is NOT_CANDIDATE. */
+#define NHDFIT_STAGES              10
+#define NHDFIT_STAGE_NOT_CANDIDATE 0    /* not in `cand`, or InitialNodeFilter drops it (NHDFIT_RF_INITIAL_FILTER)  NHDScheduler.py:235-247 */
+#define NHDFIT_STAGE_MAINTENANCE   1    /* Matcher.py:72                                                                        */
+#define NHDFIT_STAGE_HUGEPAGES     2    /* Matcher.py:77                                                                        */
+#define NHDFIT_STAGE_BUSY          3    /* Matcher.py:104 (pods that request GPUs only)                                         */
+#define NHDFIT_STAGE_GPU           4    /* Matcher.py:112-134                                                                   */
+#define NHDFIT_STAGE_CPU           5    /* Matcher.py:169-216                                                                   */
+#define NHDFIT_STAGE_NIC           6    /* Matcher.py:228-272 (the bandwidth test)                                              */
+#define NHDFIT_STAGE_PCI           7    /* PCI mode: the switch pruning removes every NIC choice, Matcher.py:294-335 (the
+                                           reference then drops the node at the intersection; this is the finer cause)         */
+#define NHDFIT_STAGE_NUMA          8    /* the GPU / CPU / NIC tuple intersection is empty, Matcher.py:337-358                  */
+#define NHDFIT_STAGE_FITS          9    /* the node survives                                                                    */
+/* counts_out [P][NHDFIT_STAGES]: nodes of the mirror per pod and stage (nodes outside `cand` count as NOT_CANDIDATE; they sum to
+ * the mirror's node count).  stage_out: NULL, or [P][n] stage codes by node index.  cand as nhdfit_find.  Explain changes nothing:
+ * not the mirror, not the busy times, not nhdfit_get_stats. */
+int nhdfit_explain(nhdfit_ctx* ctx, const nhdfit_req* reqs, uint32_t P, double now, const uint64_t* cand,
+                   uint32_t* counts_out, uint8_t* stage_out);
+/* ... for pods with 5..8 processing groups (NHDFIT_E_LIMIT as nhdfit_big_find when a NIC search runs out of budget) */
+int nhdfit_explain_big(nhdfit_ctx* ctx, const nhdfit_big_req* reqs, uint32_t P, double now, const uint64_t* cand,
+                       uint32_t* counts_out, uint8_t* stage_out);
+/* ... over every shard of a group: counts_out summed over the devices; stage_out NULL, or one [P][shard's n] buffer (or NULL)
+ * per shard.  cand as nhdfit_group_find. */
+int nhdfit_group_explain(nhdfit_group* g, const nhdfit_req* reqs, uint32_t P, double now, const uint64_t* const* cand,
+                         uint32_t* counts_out, uint8_t* const* stage_out);
+
 /* ---- request digest straight from the wire format (host code, no GPU needed) -------------------------
  * The pod's Triad libconfig text -> nhdfit_req, replacing TriadCfgParser(text, False).CfgToTopology(False)
  * (nhd/TriadCfgParser.py:337-380, called from nhd/NHDScheduler.py:262-270) followed by the getters FindNode

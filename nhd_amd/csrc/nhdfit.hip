@@ -34,6 +34,7 @@
 
 #include "seq_core.h"
 #include "wide_core.h"
+#include "explain_core.h"
 #include "dict_stream.h"
 
 using namespace nhdfit;
@@ -60,6 +61,7 @@ namespace {
 #include "seq2_kernel.h"
 #include "wide_kernel.h"
 #include "big_kernel.h"
+#include "explain_kernel.h"
 
 // ------------------------------------------------------------------------------------------------
 // host side
@@ -283,6 +285,9 @@ struct nhdfit_ctx {
     DevBuf<nhdfit_big_req> big_reqs; DevBuf<unsigned long long> big_score; DevBuf<nhdfit_big_mapping> big_maps;
     DevBuf<uint32_t> big_flags; DevBuf<nhdfit_big_placement> big_place; DevBuf<uint64_t> big_cand; DevBuf<int32_t> big_scratch;
     uint32_t wide_max_numa = 0;                            // most sockets among the wide records (sizes a big request's set tables)
+    // nhdfit_explain / nhdfit_explain_big (explain_kernel.h): buffers of their own - an explanation leaves the staged batch alone
+    DevBuf<nhdfit_wide_node> ex_views; DevBuf<int32_t> ex_slot; DevBuf<nhdfit_req> ex_reqs; DevBuf<nhdfit_big_req> ex_big_reqs;
+    DevBuf<uint32_t> ex_counts, ex_flags; DevBuf<uint64_t> ex_cand; DevBuf<uint8_t> ex_stage;
     int wide_slot(uint32_t node) const {
         auto it = std::lower_bound(wide_index.begin(), wide_index.end(), node);
         return it != wide_index.end() && *it == node ? (int)(it - wide_index.begin()) : -1;
@@ -488,6 +493,8 @@ void nhdfit_destroy(nhdfit_ctx* c) {
     c->wide.release(); c->wide_share.release(); c->wide_scratch.release(); c->wide_flags.release(); c->wide_place.release();
     c->big_reqs.release(); c->big_score.release(); c->big_maps.release(); c->big_flags.release(); c->big_place.release();
     c->big_cand.release(); c->big_scratch.release();
+    c->ex_views.release(); c->ex_slot.release(); c->ex_reqs.release(); c->ex_big_reqs.release(); c->ex_counts.release(); c->ex_flags.release();
+    c->ex_cand.release(); c->ex_stage.release();
     if (c->find_host) (void)hipHostFree(c->find_host);
     if (c->commit_host) (void)hipHostFree(c->commit_host);
     c->commit_host = nullptr;
@@ -2798,6 +2805,84 @@ int nhdfit_group_find(nhdfit_group* g, const nhdfit_req* reqs, uint32_t P, doubl
         }
     }
     if (!have_score) memset(score_out, 0, (size_t)P * 8);
+    return NHDFIT_OK;
+}
+
+// ---- explain: the stage at which each node turned each pod away (explain_kernel.h) --------------------------------------------------
+}  // extern "C"
+namespace {
+template <class R>
+int explain_run(nhdfit_ctx* c, DevBuf<R>& dreqs, const R* reqs, uint32_t P, double now, const uint64_t* cand, uint32_t* counts_out,
+                uint8_t* stage_out, uint32_t budget) {
+    if (!c) return NHDFIT_E_INVAL;
+    if (!reqs || !P || !counts_out) return fail(c, NHDFIT_E_INVAL, "explain: requests and counts_out are required");
+    if ((P + kExplainPods - 1) / kExplainPods > 65535u) return fail(c, NHDFIT_E_LIMIT, "%u requests in one explain call (<= %u)", P, 65535u * kExplainPods);
+    if (c->n && !c->ncls) return fail(c, NHDFIT_E_STATE, "set the dictionary first (nhdfit_set_dictionary: the NIC capacity classes)");
+    HIPCHK(c, hipSetDevice(c->dev));
+    { int rc_ = sync_all(c); if (rc_) return rc_; }             // (the mirror as the last call left it)
+    const uint32_t n = c->n;
+    const size_t chunks = (n + 63) / 64;
+    HIPCHK(c, dreqs.reserve(P));
+    HIPCHK(c, c->ex_counts.reserve((size_t)P * NHDFIT_STAGES));
+    HIPCHK(c, c->ex_flags.reserve(1));
+    HIPCHK(c, hipMemcpyAsync(dreqs.p, reqs, (size_t)P * sizeof *reqs, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->ex_counts.p, 0, (size_t)P * NHDFIT_STAGES * sizeof(uint32_t), c->stream));
+    HIPCHK(c, hipMemsetAsync(c->ex_flags.p, 0, sizeof(uint32_t), c->stream));
+    if (n) {
+        HIPCHK(c, c->ex_views.reserve(n));
+        HIPCHK(c, c->ex_slot.reserve(n));
+        if (stage_out) HIPCHK(c, c->ex_stage.reserve((size_t)P * n));
+        if (cand) {
+            HIPCHK(c, c->ex_cand.reserve(chunks));
+            HIPCHK(c, hipMemcpyAsync(c->ex_cand.p, cand, chunks * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+        }
+        ExplainViewArgs va;
+        memset(&va, 0, sizeof va);
+        va.p0 = c->p0.p; va.p1 = c->p1.p; va.p2 = c->p2.p; va.p3 = c->p3.p; va.p4 = c->p4.p; va.det = c->det.p; va.n = n;
+        va.wide = c->wide.p; va.n_wide = c->n_wide; va.views = c->ex_views.p; va.slot = c->ex_slot.p;
+        LAUNCH(c, k_explain_views, dim3((n + kExplainThreads - 1) / kExplainThreads), dim3(kExplainThreads), 0, c->stream, va);
+        HIPCHK(c, hipGetLastError());
+        ExplainArgs<R> ea;
+        memset(&ea, 0, sizeof ea);
+        ea.views = c->ex_views.p; ea.slot = c->ex_slot.p; ea.n = n; ea.wide = c->wide.p; ea.share = c->sharing ? c->wide_share.p : nullptr;
+        ea.reqs = dreqs.p; ea.P = P; ea.caps = c->caps.p; ea.busy_from = busy_threshold(now); ea.cand = cand ? c->ex_cand.p : nullptr;
+        ea.budget = budget; ea.counts = c->ex_counts.p; ea.stage = stage_out ? c->ex_stage.p : nullptr; ea.flags = c->ex_flags.p;
+        LAUNCH(c, k_explain<R>, dim3((n + kExplainThreads - 1) / kExplainThreads, (P + kExplainPods - 1) / kExplainPods), dim3(kExplainThreads), 0,
+               c->stream, ea);
+        HIPCHK(c, hipGetLastError());
+        if (stage_out) HIPCHK(c, hipMemcpyAsync(stage_out, c->ex_stage.p, (size_t)P * n, hipMemcpyDeviceToHost, c->stream));
+    }
+    uint32_t fl = 0;
+    HIPCHK(c, hipMemcpyAsync(counts_out, c->ex_counts.p, (size_t)P * NHDFIT_STAGES * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&fl, c->ex_flags.p, sizeof fl, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, wait_stream(c->stream));
+    if (fl) return fail(c, NHDFIT_E_LIMIT, "a big request's NIC stage ran out of search budget on some node (%u steps per NIC question, pod and node)", budget);
+    return NHDFIT_OK;
+}
+}  // namespace
+extern "C" {
+
+int nhdfit_explain(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, double now, const uint64_t* cand, uint32_t* counts_out, uint8_t* stage_out) {
+    if (!c) return NHDFIT_E_INVAL;
+    return explain_run(c, c->ex_reqs, reqs, P, now, cand, counts_out, stage_out, 0u);
+}
+
+int nhdfit_explain_big(nhdfit_ctx* c, const nhdfit_big_req* reqs, uint32_t P, double now, const uint64_t* cand, uint32_t* counts_out, uint8_t* stage_out) {
+    if (!c) return NHDFIT_E_INVAL;
+    return explain_run(c, c->ex_big_reqs, reqs, P, now, cand, counts_out, stage_out, (uint32_t)NHDFIT_BIG_NIC_BUDGET);
+}
+
+int nhdfit_group_explain(nhdfit_group* g, const nhdfit_req* reqs, uint32_t P, double now, const uint64_t* const* cand, uint32_t* counts_out,
+                         uint8_t* const* stage_out) {
+    if (!g || !reqs || !P || !counts_out) return NHDFIT_E_INVAL;
+    std::vector<uint32_t> part((size_t)P * NHDFIT_STAGES);
+    memset(counts_out, 0, part.size() * sizeof(uint32_t));
+    for (size_t k = 0; k < g->ctx.size(); ++k) {
+        nhdfit_ctx* c = g->ctx[k];
+        const int rc = nhdfit_explain(c, reqs, P, now, cand ? cand[k] : nullptr, part.data(), stage_out ? stage_out[k] : nullptr);
+        if (rc) { g->err = c->err; return rc; }
+        for (size_t j = 0; j < part.size(); ++j) counts_out[j] += part[j];
+    }
     return NHDFIT_OK;
 }
 

@@ -9,6 +9,7 @@ import numpy as np
 from . import _lib, pack
 
 SCORE_MASK = 0x7FFFFFFFFFFFFFFF
+STAGES = 10                      # NHDFIT_STAGES of include/nhdfit.h (the stage codes: matcher.STAGES)
 
 
 def _p(a: Optional[np.ndarray]):
@@ -254,6 +255,22 @@ class Engine:
         if P:
             self._chk(self.lib.nhdfit_big_find(self.ctx, _p(reqs), P, float(now), _p(cand), _p(score), _p(maps)))
         return score, maps
+
+    # ---- explain: the stage at which each node turned each pod away (nhdfit_explain / nhdfit_explain_big) ----------------
+    def explain(self, reqs: np.ndarray, now: float, cand: Optional[np.ndarray] = None, per_node: bool = False):
+        """(counts [P][STAGES] uint32, stages [P][n] uint8 or None) for ordinary (pack.REQ) or big (pack.BIG_REQ) requests.
+        Nodes outside `cand` count as NOT_CANDIDATE; nothing of the mirror changes."""
+        reqs = np.ascontiguousarray(reqs)
+        P = len(reqs)
+        counts = np.zeros((P, STAGES), np.uint32)
+        stages = np.zeros((P, self.n), np.uint8) if per_node else None
+        if cand is not None:
+            cand = np.ascontiguousarray(cand, dtype=np.uint64)
+            assert cand.shape == ((self.n + 63) // 64,)
+        if P:
+            fn = self.lib.nhdfit_explain_big if reqs.dtype == pack.BIG_REQ else self.lib.nhdfit_explain
+            self._chk(fn(self.ctx, _p(reqs), P, float(now), _p(cand), _p(counts), _p(stages)))
+        return counts, stages
 
     def big_commit(self, node: int, req: np.ndarray, mapping: np.ndarray, busy_time: float) -> np.ndarray:
         """The commit step of a big request on node `node` (ordinary or wide): updates the mirror, returns pack.BIG_PLACEMENT."""
@@ -597,6 +614,42 @@ class GroupEngine:
             if want_map:
                 maps[own] = mp[own]
         return score, (maps if want_map else None)
+
+    def explain(self, reqs: np.ndarray, now: float, cand: Optional[np.ndarray] = None, per_node: bool = False):
+        """Engine.explain over every shard: counts summed over the devices (nhdfit_group_explain for ordinary requests; big ones
+        shard by shard), stages put together in global node order."""
+        reqs = np.ascontiguousarray(reqs)
+        P = len(reqs)
+        counts = np.zeros((P, STAGES), np.uint32)
+        stages = np.zeros((P, self.n), np.uint8) if per_node else None
+        if cand is not None:
+            cand = np.ascontiguousarray(cand, dtype=np.uint64)
+        masks = [None if cand is None else np.ascontiguousarray(cand[lo // 64:(hi + 63) // 64]) for lo, hi in self._bounds]
+        if not P:
+            return counts, stages
+        if self.group is not None and reqs.dtype != pack.BIG_REQ:
+            parts = [np.zeros((P, hi - lo), np.uint8) if per_node and hi > lo else None for lo, hi in self._bounds]
+            cptr = (ctypes.c_void_p * len(self.shards))(*[None if m is None else m.ctypes.data for m in masks])
+            sptr = (ctypes.c_void_p * len(self.shards))(*[None if x is None else x.ctypes.data for x in parts])
+            rc = self.lib.nhdfit_group_explain(self.group, _p(reqs), P, float(now), cptr if cand is not None else None, _p(counts),
+                                               sptr if per_node else None)
+            if rc != 0:
+                raise _lib.NhdFitError(rc, (self.lib.nhdfit_group_last_error(self.group) or b"?").decode())
+        else:
+            parts = []
+            for k, s in enumerate(self.shards):
+                lo, hi = self._bounds[k]
+                if hi > lo:
+                    c, st = s.explain(reqs, now, cand=masks[k], per_node=per_node)
+                    counts += c
+                    parts.append(st)
+                else:
+                    parts.append(None)
+        if per_node:
+            for (lo, hi), st in zip(self._bounds, parts):
+                if st is not None:
+                    stages[:, lo:hi] = st
+        return counts, stages
 
     def big_commit(self, node: int, req, mapping, busy_time):
         k = self._shard_of(node)

@@ -111,6 +111,49 @@ _SET_ORDER_PROBES = {
 _SET_INTERSECTION_PROBE = [(1, 0, 1), (1, 1, 1), (0, 0, 0), (0, 1, 1)]
 
 
+# ---- explain: the stage at which each node turned a pod away (include/nhdfit.h NHDFIT_STAGE_*, in the reference's order) ----
+STAGES = ("NOT_CANDIDATE", "MAINTENANCE", "HUGEPAGES", "BUSY", "GPU", "CPU", "NIC", "PCI", "NUMA", "FITS")
+UNMIRRORED = 255                 # per-node stage of a node listed in HipMatcher.unmirrored (never evaluated on the device)
+_STAGE_TEXT = {"NOT_CANDIDATE": "not candidates (node group / inactive)", "MAINTENANCE": "in maintenance",
+               "HUGEPAGES": "short of hugepages", "BUSY": "busy (deployed to within the last few seconds)", "GPU": "short of GPUs",
+               "CPU": "short of CPU cores", "NIC": "short of NIC bandwidth", "PCI": "short of GPUs on the NICs' PCIe switches",
+               "NUMA": "without a NUMA-aligned placement"}
+
+
+class Explanation:
+    """Why the nodes of one FindNode call turned one pod away: `counts` (stage name -> nodes, every node charged with the first
+    stage that drops it; "FITS" = the nodes FindNode chooses among), `unmirrored` (nodes of `nl` the device does not hold -
+    they never match and are not blamed on a stage) and, when asked for, `stages` (uint8 per node in `nl` order: the stage
+    code, or UNMIRRORED).  `error`: why the pod itself could not be evaluated (a request no record can express, a NIC search
+    beyond its budget) - then no node is charged with anything: every count is 0 and `stages` is None."""
+
+    def __init__(self, counts: Dict[str, int], unmirrored: int, stages: Optional[np.ndarray] = None, error: Optional[str] = None,
+                 nodes: Optional[int] = None):
+        self.counts = counts
+        self.unmirrored = unmirrored
+        self.stages = stages
+        self.error = error
+        self.nodes = sum(counts.values()) + unmirrored if nodes is None else nodes
+
+    @property
+    def total(self) -> int:
+        """Nodes of `nl`."""
+        return self.nodes
+
+    def summary(self) -> str:
+        """The Kubernetes-style sentence: "0/65536 nodes are available: 12 in maintenance, 4100 short of hugepages, ..."."""
+        if self.error is not None:
+            return f"the pod was not evaluated against the {self.total} nodes: {self.error}."
+        parts = [f"{self.counts[s]} {_STAGE_TEXT[s]}" for s in STAGES[:-1] if self.counts.get(s)]
+        if self.unmirrored:
+            parts.append(f"{self.unmirrored} not mirrored on the device")
+        head = f"{self.counts.get('FITS', 0)}/{self.total} nodes are available"
+        return head + (": " + ", ".join(parts) + "." if parts else ".")
+
+    def __repr__(self) -> str:
+        return f"Explanation({self.summary()!r})"
+
+
 def check_interpreter_set_model() -> None:
     import itertools
     for k, want in _SET_ORDER_PROBES.items():
@@ -516,6 +559,94 @@ class HipMatcher:
         out = self._run(nl, None, pod_groups, now, sequential, reqs=reqs, big_reqs=big_reqs)
         return [(None,) if skip[i] else out[i] for i in range(len(cfg_texts))]
 
+    def ExplainNode(self, nl: Dict[str, object], top, now: Optional[float] = None, per_node: bool = False) -> Explanation:
+        """ExplainNodes for one pod."""
+        return self.ExplainNodes(nl, [top], now=now, per_node=per_node)[0]
+
+    def ExplainNodes(self, nl: Dict[str, object], tops: Sequence[object], pod_groups: Optional[Sequence[Sequence[str]]] = None,
+                     now: Optional[float] = None, per_node: bool = False) -> List[Explanation]:
+        """Why each node of `nl` turned each pod of `tops` away, counted on the device (nhdfit_explain): one Explanation per pod,
+        for the same mirror state FindNodes(nl, tops, pod_groups, now) answers from (pending changes are flushed the same way).
+        Pods with 5..8 processing groups (or hugepage requests beyond the pod tile) take nhdfit_explain_big, as FindNodes routes
+        them; wide and ENABLE_SHARING nodes are answered by their own records.  Nothing about the mirror changes.  A pod that cannot
+        be evaluated - a request no record can express, a big request whose NIC search runs out of budget - is logged and comes back
+        with `error` set and nothing charged to the cluster (strict=True raises instead); other device errors raise."""
+        n_pods = len(tops)
+        for top in tops:
+            if len(top.proc_groups) == 0 and len(nl):
+                raise IndexError("pod without processing groups (the reference fails the same way, Matcher.py:346)")
+        if n_pods == 0:
+            return []
+        if len(nl) == 0:
+            return [Explanation({s: 0 for s in STAGES}, 0, np.zeros(0, np.uint8) if per_node else None, nodes=0) for _ in range(n_pods)]
+        now = self.clock() if now is None else now
+        cand = self._sync_mirror(nl)
+        n = len(self._names)
+        # nodes the device does not hold are left out of the call (they would read as placeholders) and reported on their own
+        off = [self._index[nm] for nm in self.packer.unmirrored if nm in self._index]
+        if off:
+            bits = np.zeros(((n + 63) // 64) * 64, dtype=bool)
+            if cand is None:
+                bits[:n] = True
+            else:
+                bits[:] = np.unpackbits(cand.view(np.uint8), bitorder="little").astype(bool)
+            bits[off] = False
+            cand = np.ascontiguousarray(np.packbits(bits.reshape(-1, 64), axis=1, bitorder="little").view("<u8").reshape(-1))
+        outside = n - (n if cand is None else int(np.unpackbits(cand.view(np.uint8)).sum()))
+        n_unmirrored = sum(1 for nm in nl if nm in self.packer.unmirrored)
+        is_big = [pack.needs_general_path(top) for top in tops]
+        big_recs = {}
+        for p in range(n_pods):
+            if is_big[p]:
+                try:
+                    big_recs[p] = self.packer.digest_big(tops[p], None if pod_groups is None else pod_groups[p])
+                except pack.UnsupportedNode:               # beyond the big record too: the ordinary digest reports it (an all-zero record)
+                    if self.strict:
+                        raise
+                    is_big[p] = False
+        small_idx = [p for p in range(n_pods) if not is_big[p]]
+        errors: Dict[int, str] = {}
+        counts = np.zeros((n_pods, len(STAGES)), np.int64)
+        stages = np.zeros((n_pods, n), np.uint8) if per_node else None
+        if small_idx:
+            beyond: List[Tuple[int, str]] = []
+            reqs = self.packer.digest_many([tops[p] for p in small_idx], None if pod_groups is None else [pod_groups[p] for p in small_idx],
+                                           unsupported=beyond)
+            for k, why in beyond:                          # (an all-zero record: the kernel would charge every node NOT_CANDIDATE)
+                self.logger.error("explain: pod %d of the call cannot be expressed as a request record and is not evaluated: %s", small_idx[k], why)
+                errors[small_idx[k]] = f"it cannot be expressed as a request record ({why})"
+            c, st = self.engine.explain(reqs, now, cand=cand, per_node=per_node)
+            counts[small_idx] = c
+            if per_node:
+                stages[small_idx] = st
+        if big_recs:
+            big_idx = sorted(big_recs)
+            try:
+                c, st = self.engine.explain(np.array([big_recs[p] for p in big_idx], dtype=pack.BIG_REQ), now, cand=cand, per_node=per_node)
+                counts[big_idx] = c
+                if per_node:
+                    stages[big_idx] = st
+            except NhdFitError as e:                       # (NHDFIT_E_LIMIT: a NIC search beyond its budget - nothing is known for these pods)
+                if self.strict:
+                    raise
+                self.logger.error("explain: the pods with 5..8 processing groups of the call are not evaluated (%s)", e)
+                for p in big_idx:
+                    errors[p] = f"the device could not evaluate it ({e})"
+        counts[:, 0] -= outside                            # (the kernel counts every node of the mirror outside `cand` as NOT_CANDIDATE)
+        order = None
+        if per_node:
+            order = np.fromiter((self._index[nm] for nm in nl), dtype=np.int64, count=len(nl))
+            if off:
+                stages[:, off] = UNMIRRORED
+        out = []
+        for p in range(n_pods):
+            if p in errors:
+                out.append(Explanation({s: 0 for s in STAGES}, n_unmirrored, None, error=errors[p], nodes=len(nl)))
+                continue
+            out.append(Explanation({s: int(counts[p, k]) for k, s in enumerate(STAGES)}, n_unmirrored,
+                                   stages[p, order] if per_node else None, nodes=len(nl)))
+        return out
+
     @property
     def unmirrored(self) -> Dict[str, str]:
         """Nodes NEITHER layout holds (more than four sockets, more than 128 physical cores per socket ...; name -> reason): they never
@@ -536,31 +667,9 @@ class HipMatcher:
                 self._warned.add(name)
                 self.logger.warning("node %s is not mirrored on the device and will never be selected: %s", name, why)
 
-    def _run(self, nl, tops, pod_groups, now, sequential, reqs=None, apply=False, big_reqs=None):
-        try:
-            return self._run_checked(nl, tops, pod_groups, now, sequential, reqs, apply, big_reqs)
-        except NhdFitError as e:
-            if self.strict:
-                raise
-            n_pods = len(tops) if reqs is None else len(reqs)
-            self.logger.error("FindNode: the device path failed (%s): %d pod(s) answered (None,)", e, n_pods)
-            self._mirror_foreign = True                   # whatever the mirror holds now, rebuild it before the next call
-            self._last_subset = None
-            self.last_placements = [None] * n_pods
-            return [(None,) for _ in range(n_pods)]
-
-    def _run_checked(self, nl, tops, pod_groups, now, sequential, reqs=None, apply=False, big_reqs=None):
-        if reqs is None:
-            if not tops:
-                self.last_placements = []
-                return []
-            for top in tops:
-                if len(top.proc_groups) == 0 and len(nl):
-                    raise IndexError("pod without processing groups (the reference fails the same way, Matcher.py:346)")
-        n_pods = len(tops) if reqs is None else len(reqs)
-        if len(nl) == 0:
-            return [(None,) for _ in range(n_pods)]
-        now = self.clock() if now is None else now
+    def _sync_mirror(self, nl: Dict[str, object]) -> Optional[np.ndarray]:
+        """Bring the device mirror up to what the node objects say before a call on `nl` (pending deltas and dirty nodes of the
+        attached dict flushed, or `nl` packed anew); returns the candidate mask of `nl` (None: every mirrored node)."""
         cand = None
         known = False
         if self._attached is not None:
@@ -588,6 +697,34 @@ class HipMatcher:
             self._full_upload(nl)
             self._mirror_foreign = self._attached is not None
         self._warn_unmirrored()
+        return cand
+
+    def _run(self, nl, tops, pod_groups, now, sequential, reqs=None, apply=False, big_reqs=None):
+        try:
+            return self._run_checked(nl, tops, pod_groups, now, sequential, reqs, apply, big_reqs)
+        except NhdFitError as e:
+            if self.strict:
+                raise
+            n_pods = len(tops) if reqs is None else len(reqs)
+            self.logger.error("FindNode: the device path failed (%s): %d pod(s) answered (None,)", e, n_pods)
+            self._mirror_foreign = True                   # whatever the mirror holds now, rebuild it before the next call
+            self._last_subset = None
+            self.last_placements = [None] * n_pods
+            return [(None,) for _ in range(n_pods)]
+
+    def _run_checked(self, nl, tops, pod_groups, now, sequential, reqs=None, apply=False, big_reqs=None):
+        if reqs is None:
+            if not tops:
+                self.last_placements = []
+                return []
+            for top in tops:
+                if len(top.proc_groups) == 0 and len(nl):
+                    raise IndexError("pod without processing groups (the reference fails the same way, Matcher.py:346)")
+        n_pods = len(tops) if reqs is None else len(reqs)
+        if len(nl) == 0:
+            return [(None,) for _ in range(n_pods)]
+        now = self.clock() if now is None else now
+        cand = self._sync_mirror(nl)
         if reqs is not None and self.packer.sharing:       # digested from config texts, and speed_used prices the NICs (nhd/Node.py:754)
             for arr in (reqs, *(big_reqs or {}).values()):
                 for rq in (arr if arr.ndim else [arr]):

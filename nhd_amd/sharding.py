@@ -4,6 +4,8 @@ process per GPU, `nhdfit_group_find` for one process driving several GPUs).  Thi
 arithmetic around it: shard bounds, the order-preserving uint64 <-> int64 map (for reducers without uint64 MAX), and mode B
 with one process per GPU (`schedule_batch_sharded`) over a plain transport object - `RcclTransport` is the product's: the
 communicator of the rank's own context behind the C-ABI (nhdfit_comm_sendrecv / nhdfit_comm_allreduce_sum_u8: RCCL over xGMI).
+Explanations (nhdfit_explain, Engine.explain) are per shard: each rank explains the nodes of its own context, and the caller sums
+the ranks' per-pod stage counts (there is no cross-rank reduction of them).
 Nothing here imports torch.
 """
 from __future__ import annotations
