@@ -63,7 +63,18 @@ class Engine:
         self._dict_version = -1
 
     def upload(self, table: pack.NodeTable, global_base: int = 0, first: int = 0, capacity: Optional[int] = None):
-        """Full upload (first == 0 and nothing uploaded yet) or delta upload of `table` at `first`."""
+        """Full upload (first == 0 and nothing uploaded yet) or delta upload of `table` at `first`.  Under ENABLE_SHARING every slice
+        carries its nodes' speed_used records (`table.share`, as download() returns them); a slice without them raises before anything
+        on the device changes.  (A mirror that is to stop sharing is emptied first: reset_nodes.)"""
+        sharing = getattr(self, "_share", None) is not None
+        whole = first == 0 and table.n >= self.n
+        if sharing and table.n and not table.share:
+            # (a table packed with the constant off, or a restore from a download that lost the records: never continue with the
+            #  shipped arithmetic silently - and never after nhdfit_wide_upload has already switched the sharing arithmetic off)
+            raise _lib.NhdFitError(-5, "ENABLE_SHARING: the uploaded slice [%d, %d) carries no speed_used records" % (first, first + table.n))
+        if table.share and len(table.share) != table.n:
+            missing = next(i for i in range(table.n) if i not in table.share)
+            raise _lib.NhdFitError(-5, "ENABLE_SHARING: node %d of the uploaded slice carries no speed_used record" % (first + missing))
         cap = max(capacity or 0, first + table.n)
         self._chk(self.lib.nhdfit_reserve_nodes(self.ctx, cap, global_base))
         arrs = [np.ascontiguousarray(x) for x in (table.p0, table.p1, table.p2, table.p3, table.p4, table.detail)]
@@ -71,12 +82,12 @@ class Engine:
         if table.origin is not None and table.n:
             origin = np.ascontiguousarray(table.origin)          # (bound to a name: _p hands out a bare address)
             self._chk(self.lib.nhdfit_upload_origin(self.ctx, first, table.n, _p(origin)))
-        sharing = getattr(self, "_share", None) is not None
-        whole = first == 0 and table.n >= self.n
         if sharing and not whole and self.n_wide:
             # ENABLE_SHARING, delta upload: device-side commits (wide_commit, schedule_batch) added rx / tx to speed_used records this
             # host copy has never seen - fetch them before nhdfit_wide_upload switches sharing off, so that the nodes OUTSIDE the slice
-            # go back up as the device left them (a wide record showing the cores taken beside a speed_used that forgot the claim)
+            # go back up as the device left them (a wide record showing the cores taken beside a speed_used that forgot the claim).
+            # The fetch covers the slice's own nodes too, speculative commits of an apply=False batch included; the slice's records
+            # are written over them below, so a restore puts back what it carries
             dev = self.wide_share_download()
             if len(dev):
                 self._share[:len(dev)] = dev
@@ -93,22 +104,12 @@ class Engine:
                 if sharing:
                     grown[:len(self._share)] = self._share
                 self._share = grown
-            missing = [i for i in range(table.n) if i not in table.share] if len(table.share) != table.n else []
-            if missing:
-                raise _lib.NhdFitError(-5, "ENABLE_SHARING: node %d of the uploaded slice carries no speed_used record" % (first + missing[0]))
             for i, rec in table.share.items():
                 self._share[first + i] = rec
             if self.n_wide != self.n:
                 raise _lib.NhdFitError(-5, "ENABLE_SHARING: a node of the mirror is not held by the general path")
             share = np.ascontiguousarray(self._share[:self.n])
             self._chk(self.lib.nhdfit_wide_share_upload(self.ctx, _p(share), len(share)))
-        elif sharing and whole:
-            self._share = None                                      # the whole mirror replaced by a table without speed_used records: sharing is off
-            self._chk(self.lib.nhdfit_wide_share_upload(self.ctx, None, 0))
-        elif sharing and table.n:
-            # a slice without speed_used records under ENABLE_SHARING (a node that no longer fits a wide record, a table packed with the
-            # constant off): nhdfit_wide_upload has switched the sharing arithmetic off - never continue with the shipped arithmetic silently
-            raise _lib.NhdFitError(-5, "ENABLE_SHARING: the uploaded slice [%d, %d) carries no speed_used records" % (first, first + table.n))
         self.global_base = global_base
 
     def wide_count(self) -> int:
@@ -155,8 +156,17 @@ class Engine:
             self._chk(self.lib.nhdfit_apply_deltas(self.ctx, _p(deltas), len(deltas), _p(status)))
         return status
 
+    @property
+    def sharing(self) -> bool:
+        """ENABLE_SHARING: the mirror holds speed_used records beside its wide records."""
+        return getattr(self, "_share", None) is not None
+
     def reset_nodes(self):
+        """An empty mirror: whether it shares NICs is up to the next upload (a table with or without speed_used records)."""
         self._chk(self.lib.nhdfit_set_node_count(self.ctx, 0))
+        if getattr(self, "_share", None) is not None:
+            self._chk(self.lib.nhdfit_wide_share_upload(self.ctx, None, 0))
+            self._share = None
         self.n = 0
         self.n_wide = 0
 
@@ -286,7 +296,13 @@ class Engine:
         t.origin = None                                     # not read back: uploading this table leaves the origin records alone
         self._chk(self.lib.nhdfit_download_nodes(self.ctx, first, count, _p(t.p0), _p(t.p1), _p(t.p2), _p(t.p3), _p(t.p4), _p(t.detail)))
         if self.n_wide:
-            t.wide = {int(w["index"]) - first: w.copy() for w in self.wide_download() if first <= int(w["index"]) < first + count}
+            recs = self.wide_download()
+            t.wide = {int(w["index"]) - first: w.copy() for w in recs if first <= int(w["index"]) < first + count}
+            if getattr(self, "_share", None) is not None:           # ENABLE_SHARING: the NICs' speed_used as the device's commits left them,
+                share = self.wide_share_download()                  # in the order of the wide records - so that upload(download()) restores them
+                if len(share) != len(recs):
+                    raise _lib.NhdFitError(-5, "ENABLE_SHARING: %d speed_used records for %d wide records" % (len(share), len(recs)))
+                t.share = {int(w["index"]) - first: share[k].copy() for k, w in enumerate(recs) if first <= int(w["index"]) < first + count}
         return t
 
     # ---- pipelined --------------------------------------------------------------------
@@ -435,9 +451,13 @@ class GroupEngine:
         raise IndexError(i)
 
     def upload(self, table: pack.NodeTable, global_base: int = 0, first: int = 0, capacity: Optional[int] = None):
-        """Full upload (first == 0: defines the shard bounds) or delta upload of a run of nodes at `first`."""
+        """Full upload (first == 0: defines the shard bounds) or delta upload of a run of nodes at `first` (Engine.upload: the
+        speed_used records under ENABLE_SHARING)."""
         from .sharding import shard_bounds
         if first == 0 and (not self._bounds or table.n >= self.n):
+            if table.n and not table.share and any(getattr(s, "sharing", False) for s in self.shards):
+                # (the shards are emptied below: Engine.upload would not see that this table drops the speed_used records)
+                raise _lib.NhdFitError(-5, "ENABLE_SHARING: the uploaded table carries no speed_used records (reset_nodes first to stop sharing)")
             n = table.n
             self._bounds = [shard_bounds(n, len(self.shards), r) for r in range(len(self.shards))]
             for s, (lo, hi) in zip(self.shards, self._bounds):
@@ -687,6 +707,10 @@ class GroupEngine:
                 getattr(out, f)[i - first:j - first] = getattr(part, f)
             for q, w in (part.wide or {}).items():
                 out.wide[q + i - first] = w
+            if part.share:                                          # ENABLE_SHARING: the shards' speed_used records, as the wide ones
+                out.share = out.share or {}
+                for q, r in part.share.items():
+                    out.share[q + i - first] = r
             i = j
         return out
 

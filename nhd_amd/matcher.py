@@ -208,6 +208,7 @@ class HipMatcher:
         # node groups take turns in the pending list, each group with its own filtered dict (nhd/NHDScheduler.py:235-247)
         self._last_subset: Optional[Dict[tuple, List[Tuple[List[str], np.ndarray]]]] = None
         self._subset_count = self._subset_names = 0
+        self._digest_cache: Optional[Tuple[object, np.ndarray]] = None     # (topology, request record) of the last one-pod FindNode
 
     # ---- mirror maintenance -------------------------------------------------------------
     def attach(self, nodes: Dict[str, object]) -> None:
@@ -265,8 +266,15 @@ class HipMatcher:
         bt = float(node.busy_time if busy_time is None and node is not None else busy_time)
         if pack.needs_general_path(top):                                                # a pod with 5..8 processing groups (or beyond the hugepage table): the general path's commit step
             return self._commit_big(i, node, self.packer.digest_big(top), self._mapping_record(mapping, big=True), bt)
-        cached = getattr(self, "_digest_cache", None)                 # the record FindNode made of this very topology a moment ago (the scheduler
-        req = cached[1] if cached is not None and cached[0] is top else self.packer.digest(top)   # commits what it has just matched, nhd/NHDScheduler.py:277-304)
+        cached, self._digest_cache = self._digest_cache, None         # the record FindNode made of this very topology a moment ago (the scheduler
+        if cached is not None and cached[0] is top:                   # commits what it has just matched, nhd/NHDScheduler.py:277-304) - spent here
+            req = cached[1]
+            if self.packer.sharing:                                   # its speeds reach speed_used as digest() would have noted them (a full re-pack
+                for g in range(int(req["n_groups"])):                 # since the find started share_exact afresh)
+                    self.packer._note_share_value(req["rx"][g])
+                    self.packer._note_share_value(req["tx"][g])
+        else:
+            req = self.packer.digest(top)
         if self.packer.sharing and int(req["flags"]) & pack.RF_NIC_SPLIT and not self.packer.share_exact:
             # (the cached record was admitted when every speed in the mirror was still a multiple of 2^-20; one that is not arrived since)
             raise pack.UnsupportedNode("a processing group with several RX / TX cores (ENABLE_SHARING), and the mirror's speeds are no longer all "
@@ -420,6 +428,7 @@ class HipMatcher:
 
     def _full_upload(self, nl: Dict[str, object]) -> None:
         self._last_subset = None                           # node indices change
+        self._digest_cache = None                          # (a re-pack notes the mirror's speeds afresh, Packer.share_exact)
         table = self.packer.pack_nodes(nl)
         self._table = table
         self._names = table.names
@@ -773,7 +782,7 @@ class HipMatcher:
             beyond: List[Tuple[int, str]] = []
             reqs = self.packer.digest_many(tops, pod_groups, unsupported=beyond)
             if n_pods == 1 and not beyond:
-                self._digest_cache = (tops[0], reqs[0])     # CommitPlacement of the same topology object does not digest it again
+                self._digest_cache = (tops[0], reqs[0].copy())     # CommitPlacement of the same topology object does not digest it again
             for i, why in beyond:
                 self.logger.error("pod %d of the call cannot be expressed as a request record and is answered (None,): %s", i, why)
         elif pod_groups is not None:                       # requests digested from config texts: InitialNodeFilter in the kernel

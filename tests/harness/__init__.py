@@ -391,6 +391,7 @@ class HarnessEngine:
         self.table = None
         self.wide = {}                                  # local index -> nhdfit_wide_node (the general path's records)
         self.share = {}                                 # local index -> nhdfit_wide_share (ENABLE_SHARING: one per node, all nodes wide)
+        self.sharing = False                            # Engine._share is not None: a table with speed_used records went up (until reset_nodes)
         self.last_wide_places = {}
 
     @property
@@ -430,9 +431,18 @@ class HarnessEngine:
         self.table = None
         self.wide = {}
         self.share = {}
+        self.sharing = False
 
     def upload(self, table, global_base=0, first=0, capacity=None):
-        if first == 0 and (self.table is None or table.n >= self.n):
+        from nhd_amd._lib import NhdFitError
+        whole = first == 0 and (self.table is None or table.n >= self.n)
+        if self.sharing and table.n and not table.share:      # Engine.upload's checks, before anything changes
+            raise NhdFitError(-5, "ENABLE_SHARING: the uploaded slice [%d, %d) carries no speed_used records" % (first, first + table.n))
+        if table.share and len(table.share) != table.n:
+            raise NhdFitError(-5, "ENABLE_SHARING: a node of the uploaded slice carries no speed_used record")
+        if table.share:
+            self.sharing = True
+        if whole:
             self.table = pack.NodeTable(list(table.names), *[np.array(getattr(table, f)) for f in
                                                             ("p0", "p1", "p2", "p3", "p4", "detail")],
                                         np.zeros(table.n, pack.ORIGIN) if table.origin is None else np.array(table.origin))
@@ -569,4 +579,6 @@ class HarnessEngine:
         out.wide = {i - first: np.array(r) for i, r in self.wide.items() if first <= i < first + count}
         for q, r in out.wide.items():
             r["index"] = q + first
+        if self.share:                                  # ENABLE_SHARING: the speed_used records as the commits left them (Engine.download)
+            out.share = {i - first: np.array(r) for i, r in self.share.items() if first <= i < first + count}
         return out
