@@ -13,6 +13,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 SO = os.path.join(HERE, "libnhdoracle.so")
 MAXG = 8
+STAGES = 10                 # include/nhdfit.h NHDFIT_STAGES
 
 ONODE = np.dtype([("numa_nodes", "<i4"), ("smt", "<i4"), ("n_scan", "<i4"), ("core_off", "<i4"), ("n_cores", "<i4"),
                   ("gpu_off", "<i4"), ("n_gpus", "<i4"), ("nic_off", "<i4"), ("n_nics", "<i4"), ("hp_free", "<i4"),
@@ -196,19 +197,29 @@ class Cluster:
                 p["groups"] = self.group_ids.bits(pod_groups[i])
         return pods
 
-    def find(self, pods, now, want_feas=True, threads=1):
-        L = lib()
+    @staticmethod
+    def _threads(threads):
         threads = max(1, min(int(threads), usable_cpus()))   # never more threads than this process may run on (CPU set, cgroup quota)
         os.environ["OMP_NUM_THREADS"] = str(threads)
         try:
             ctypes.CDLL("libgomp.so.1").omp_set_num_threads(int(threads))
         except OSError:
             pass
+
+    def _oc(self):
+        """The C view of the records (the arrays it points into are kept on the returned object)."""
         a = {k: np.ascontiguousarray(v) for k, v in self.arrays.items()}
         nodes = np.ascontiguousarray(self.nodes)
         oc = _OCluster(nodes.ctypes.data, self.n, *[a[k].ctypes.data for k in
                        ("core_used", "core_socket", "core_sibling", "gpu_used", "gpu_numa", "gpu_sw", "nic_numa",
                         "nic_speed", "nic_pods", "nic_sw")])
+        oc._keep = (a, nodes)
+        return oc
+
+    def find(self, pods, now, want_feas=True, threads=1):
+        L = lib()
+        self._threads(threads)
+        oc = self._oc()
         pods = np.ascontiguousarray(pods)
         winner = np.zeros(len(pods), np.int64)
         feas = np.zeros((len(pods), self.n), np.uint8) if want_feas else None
@@ -216,3 +227,28 @@ class Cluster:
                       ctypes.c_double(now), winner.ctypes.data_as(ctypes.c_void_p),
                       feas.ctypes.data_as(ctypes.c_void_p) if want_feas else None)
         return winner, feas
+
+    def explain(self, pods, now, cand=None, per_node=False, threads=1):
+        """The stage (include/nhdfit.h NHDFIT_STAGE_*) at which the reference drops each node for each pod (oracle_explain):
+        (counts [P][10] int64, stages [P][n] uint8 or None).  `cand`: n booleans; nodes outside it are NOT_CANDIDATE."""
+        L = lib()
+        self._threads(threads)
+        oc = self._oc()
+        pods = np.ascontiguousarray(pods)
+        if cand is not None:
+            cand = np.ascontiguousarray(np.asarray(cand, dtype=bool).astype(np.uint8))
+            assert cand.shape == (self.n,)
+        counts = np.zeros((len(pods), STAGES), np.int64)
+        stages = np.zeros((len(pods), self.n), np.uint8) if per_node else None
+        L.oracle_explain.restype = ctypes.c_int64
+        bad = L.oracle_explain(ctypes.byref(oc), pods.ctypes.data_as(ctypes.c_void_p), ctypes.c_int64(len(pods)),
+                               ctypes.c_double(now), None if cand is None else cand.ctypes.data_as(ctypes.c_void_p),
+                               counts.ctypes.data_as(ctypes.c_void_p),
+                               None if stages is None else stages.ctypes.data_as(ctypes.c_void_p))
+        assert bad == 0, f"{bad} (pod, node) pairs beyond the oracle's records"
+        return counts, stages
+
+    def subset(self, keep):
+        """The cluster of the nodes where `keep` (n booleans) is set, in their order (the records are shared, not copied)."""
+        keep = np.asarray(keep, dtype=bool)
+        return Cluster(self.nodes[keep], self.arrays, self.group_ids)

@@ -307,5 +307,185 @@ int oracle_commit(const ocluster* c, int64_t idx, const opod* p, const int32_t* 
 }
 
 
+/* ---- explain: the stage at which the reference drops a node ----------------------------------------------------------
+ * Reference lines followed (the stages as tests/explain_reference.py derives them from the reference's own lists):
+ *   InitialNodeFilter -> NOT_CANDIDATE                       nhd/NHDScheduler.py:235-247
+ *   invalid map type -> every node NOT_CANDIDATE             nhd/Matcher.py:45-47
+ *   FilterPodResources -> MAINTENANCE, HUGEPAGES             nhd/Matcher.py:65-84
+ *   busy GPU pod -> BUSY; empty GPU list -> GPU               nhd/Matcher.py:95-149
+ *   empty CPU list (all G+1 tuples) -> CPU                   nhd/Matcher.py:152-222
+ *   empty NIC list (all G tuples, all NIC picks) -> NIC      nhd/Matcher.py:224-280
+ *   PCI pruning of the NIC list, then the tuple intersection nhd/Matcher.py:294-335, 337-391
+ *     an empty intersection is PCI when the pruned NIC list is empty (PCI map type only), else NUMA
+ * Unlike oracle_feasible, which merges the lists in one loop and stops at the first combination that fits, each list is
+ * decided over ALL assignments on its own before the next is looked at.  Sharing is off (NICs priced without speed_used). */
+enum { ST_NOT_CANDIDATE, ST_MAINTENANCE, ST_HUGEPAGES, ST_BUSY, ST_GPU, ST_CPU, ST_NIC, ST_PCI, ST_NUMA, ST_FITS, ST_COUNT };
+
+typedef struct {
+    int U, G, K[MAXU];
+    double cap[MAXU][MAXNIC];
+    int sw[MAXU][MAXNIC];
+    int free_gpu_on_sw[MAXU * MAXNIC];   /* free GPUs on the switch of NIC (u, k), flattened u * MAXNIC + k */
+} nic_view;
+
+/* The NIC list's verdict for one assignment a[0..G): bit 0 = some choice of one NIC per group leaves every NIC's RX and TX
+ * capacity non-negative (Matcher.py:246-276), bit 1 = such a choice also survives the PCI pruning (Matcher.py:300-322).  Stops
+ * as soon as both are known (or bit 0, when pci is not asked). */
+static int nic_verdict(const nic_view* v, const opod* p, const int* a, int pci) {
+    const int G = v->G;
+    for (int g = 0; g < G; ++g) if (v->K[a[g]] == 0) return 0;
+    int pick[MAXG] = {0}, out = 0;
+    for (;;) {
+        /* capacity: for every NIC, the groups that chose it must fit in what it has free */
+        int fine = 1;
+        for (int g = 0; g < G && fine; ++g) {
+            double rx = v->cap[a[g]][pick[g]], tx = rx;
+            for (int h = 0; h < G; ++h)
+                if (a[h] == a[g] && pick[h] == pick[g]) { rx -= p->rx[h]; tx -= p->tx[h]; }
+            if (rx < 0 || tx < 0) fine = 0;
+        }
+        if (fine) {
+            out |= 1;
+            if (!pci) return out;
+            int sw_ok = 1;
+            for (int g = 0; g < G && sw_ok; ++g) {
+                const int s = v->sw[a[g]][pick[g]];
+                int need = 0;
+                for (int h = 0; h < G; ++h) if (v->sw[a[h]][pick[h]] == s) need++;
+                if (v->free_gpu_on_sw[a[g] * MAXNIC + pick[g]] < need) sw_ok = 0;
+            }
+            if (sw_ok) return 3;
+        }
+        int pos = G - 1;
+        while (pos >= 0) { if (++pick[pos] < v->K[a[pos]]) break; pick[pos] = 0; --pos; }
+        if (pos < 0) return out;
+    }
+}
+
+/* Stage code (include/nhdfit.h NHDFIT_STAGE_*) of node idx for pod p; -1 for a node or pod beyond the records. */
+int oracle_stage(const ocluster* c, int64_t idx, const opod* p, double now) {
+    const onode* nd = &c->nodes[idx];
+    const int U = nd->numa_nodes, G = p->G;
+    if (p->use_filter && !((nd->groups & p->groups) && nd->active)) return ST_NOT_CANDIDATE;
+    if (p->map_type != 1 && p->map_type != 2) return ST_NOT_CANDIDATE;
+    if (nd->maintenance) return ST_MAINTENANCE;
+    if (p->hp > nd->hp_free) return ST_HUGEPAGES;
+    if (G < 1 || G > MAXG || U < 1 || U > MAXU) return -1;
+
+    int sum_g = 0;
+    for (int g = 0; g < G; ++g) sum_g += p->n_gpus[g];
+    if (sum_g > 0 && (now - nd->busy_time) < 30.0) return ST_BUSY;
+
+    const int nA = ipow(U, G);
+    int a[MAXG + 1];
+
+    /* GPU list: every assignment of the groups to NUMA nodes whose per-node GPU totals fit the free GPUs there */
+    int free_g[MAXU] = {0};
+    for (int q = 0; q < nd->n_gpus; ++q)
+        if (!c->gpu_used[nd->gpu_off + q]) free_g[c->gpu_numa[nd->gpu_off + q]]++;
+    uint8_t gpu_ok[65536];
+    int any = 0;
+    for (int code = 0; code < nA; ++code) {
+        digits(code, U, G, a);
+        int tot[MAXU] = {0}, ok = 1;
+        for (int g = 0; g < G; ++g) tot[a[g]] += p->n_gpus[g];
+        for (int u = 0; u < U; ++u) if (tot[u] > free_g[u]) ok = 0;
+        gpu_ok[code] = (uint8_t)ok;
+        any |= ok;
+    }
+    if (!any) return ST_GPU;
+
+    /* CPU list: every (G+1)-tuple - the groups, then the misc cores - whose per-node physical-core totals fit */
+    int free_c[MAXU] = {0};
+    for (int k = 0; k < nd->n_scan; ++k) {
+        const int o = nd->core_off + k;
+        if (c->core_used[o]) continue;
+        if (nd->smt && c->core_used[nd->core_off + c->core_sibling[o]]) continue;
+        free_c[c->core_socket[o]]++;
+    }
+    int want[MAXG + 1];
+    for (int g = 0; g < G; ++g)
+        want[g] = nd->smt ? (p->proc_smt[g] ? half_up(p->n_proc[g]) : p->n_proc[g]) +
+                            (p->help_smt[g] ? half_up(p->n_help[g]) : p->n_help[g])
+                          : p->n_proc[g] + p->n_help[g];
+    want[G] = nd->smt && p->misc_smt_truthy ? half_up(p->n_misc) : p->n_misc;
+    uint8_t cpu_ok[65536];
+    memset(cpu_ok, 0, (size_t)nA);
+    any = 0;
+    for (int code = 0; code < nA * U; ++code) {
+        digits(code, U, G + 1, a);                 /* a[0..G) the groups, a[G] the misc cores; code / U indexes the groups */
+        int tot[MAXU] = {0}, ok = 1;
+        for (int g = 0; g <= G; ++g) tot[a[g]] += want[g];
+        for (int u = 0; u < U; ++u) if (tot[u] > free_c[u]) ok = 0;
+        if (ok) { cpu_ok[code / U] = 1; any = 1; }
+    }
+    if (!any) return ST_CPU;
+
+    /* NIC records per NUMA node in node.nics order (Node.py:283-296, sharing off); switch GPU counts (Node.py:266-273) */
+    nic_view v;
+    v.U = U; v.G = G;
+    for (int u = 0; u < MAXU; ++u) v.K[u] = 0;
+    for (int k = 0; k < nd->n_nics; ++k) {
+        const int o = nd->nic_off + k, u = c->nic_numa[o];
+        if (u < 0 || u >= U || v.K[u] >= MAXNIC) continue;
+        const int j = v.K[u]++;
+        v.cap[u][j] = c->nic_pods[o] > 0 ? 0.0 : c->nic_speed[o] * 0.9;
+        v.sw[u][j] = c->nic_sw[o];
+        int have = 0;
+        for (int q = 0; q < nd->n_gpus; ++q)
+            if (!c->gpu_used[nd->gpu_off + q] && c->gpu_sw[nd->gpu_off + q] == c->nic_sw[o]) have++;
+        v.free_gpu_on_sw[u * MAXNIC + j] = have;
+    }
+    const int pci = p->map_type == 2;
+
+    /* the intersection first (it settles FITS), then the NIC list on its own and the pruned list on its own */
+    int nic_any = 0, pruned_any = 0;
+    for (int code = 0; code < nA; ++code) {
+        if (!gpu_ok[code] || !cpu_ok[code]) continue;
+        digits(code, U, G, a);
+        const int r = nic_verdict(&v, p, a, pci);
+        nic_any |= r & 1;
+        pruned_any |= pci ? (r >> 1) & 1 : r & 1;
+        if (pci ? (r & 2) : (r & 1)) return ST_FITS;
+    }
+    for (int code = 0; code < nA && !(nic_any && pruned_any); ++code) {
+        if (gpu_ok[code] && cpu_ok[code]) continue;                          /* asked above */
+        digits(code, U, G, a);
+        const int r = nic_verdict(&v, p, a, pci);
+        nic_any |= r & 1;
+        pruned_any |= pci ? (r >> 1) & 1 : r & 1;
+    }
+    if (!nic_any) return ST_NIC;
+    if (pci && !pruned_any) return ST_PCI;
+    return ST_NUMA;
+}
+
+/* counts[P][ST_COUNT] (int64); stages (optional) [P][n] bytes; cand (optional) n bytes, 0 = outside the candidate mask
+ * (NOT_CANDIDATE).  Returns the number of (pod, node) pairs oracle_stage could not judge (stage byte 255). */
+int64_t oracle_explain(const ocluster* c, const opod* pods, int64_t P, double now, const uint8_t* cand, int64_t* counts,
+                       uint8_t* stages) {
+    const int64_t B = 256, nb = (c->n + B - 1) / B;
+    int64_t bad = 0;
+    memset(counts, 0, sizeof(int64_t) * (size_t)(P * ST_COUNT));
+#pragma omp parallel for schedule(dynamic, 1) reduction(+:bad)
+    for (int64_t t = 0; t < P * nb; ++t) {
+        const int64_t p = t / nb, lo = (t % nb) * B, hi = lo + B < c->n ? lo + B : c->n;
+        int64_t local[ST_COUNT] = {0};
+        for (int64_t i = lo; i < hi; ++i) {
+            const int s = (cand && !cand[i]) ? ST_NOT_CANDIDATE : oracle_stage(c, i, &pods[p], now);
+            if (s < 0) { bad++; if (stages) stages[p * c->n + i] = 255; continue; }
+            local[s]++;
+            if (stages) stages[p * c->n + i] = (uint8_t)s;
+        }
+        for (int k = 0; k < ST_COUNT; ++k) {
+            if (!local[k]) continue;
+#pragma omp atomic
+            counts[p * ST_COUNT + k] += local[k];
+        }
+    }
+    return bad;
+}
+
+
 int oracle_sizeof_node(void) { return (int)sizeof(onode); }
 int oracle_sizeof_pod(void) { return (int)sizeof(opod); }

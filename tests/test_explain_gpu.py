@@ -1,8 +1,8 @@
 """nhdfit_explain on the MI355X: the device's stage for every (pod, node) against the reference's stored stages on the
-golden fixtures, its counts against nhdfit_find's verdict bitmap and a vectorised host computation at BASELINE shapes, the
+golden fixtures, its counts against nhdfit_find's verdict bitmap and a vectorised host computation at BASELINE shapes, its counts
+and per-node stages against the C stage oracle (oracle_explain) on random, wide, big-pod, masked and sharded inputs, the
 absence of side effects and the group entry (`pytest -m gpu`); and k_explain's resources (hipcc only, no GPU).  Nothing here reads the
 reference tree: its answers come from tests/golden/refanswers/tests.test_explain_reference.json."""
-import itertools
 import os
 import re
 import shutil
@@ -12,14 +12,18 @@ import numpy as np
 import pytest
 
 from nhd_amd import pack
-from nhd_amd.engine import Engine
+from nhd_amd.engine import Engine, GroupEngine
 from nhd_amd.matcher import STAGES, HipMatcher
+from oracle import coracle
 from oracle import nhd_oracle as O
 from tests import explain_check, util
+from tests.test_big_core import big_spec
 from workload import planes, refmodel, synth
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FITS = STAGES.index("FITS")
+LATE = [STAGES.index(s) for s in ("NIC", "PCI", "NUMA")]
+WHOLE_MATRIX_CPUS = 8             # the whole-matrix oracle comparisons below skip, visibly, on hosts with fewer usable CPUs
 
 
 def unpack_bitmap(bm, n):
@@ -35,61 +39,6 @@ def test_golden_stages_equal_the_reference(golden):
     path = explain_check.GOLDENS[explain_check.IDS.index(golden)]
     got = explain_check.explain(path, lambda clock: HipMatcher(device=0, clock=lambda: clock))
     assert got == explain_check.stored(golden)
-
-
-def host_stages_upto_cpu(table, reqs, now):
-    """Stages 0..5 per (pod, node) by numpy over the planes (ordinary nodes, ordinary requests); 6 stands for "beyond the CPU
-    stage".  The GPU and CPU stages are asked per distinct (node free resources, request demand) pair."""
-    n = table.n
-    flags = table.p2["flags"].astype(np.int64)
-    U = table.detail["numa_nodes"].astype(np.int64)
-    smt = (flags & pack.NF_SMT) != 0
-    free = table.p0["t0"] & table.p1["t1"]
-    fc = np.stack([np.array([bin(int(x)).count("1") for x in free[:, u]]) for u in range(2)], 1)
-    gmask = table.p2["gpu_free"].astype(np.int64)
-    g1 = table.p2["gpu_numa1"].astype(np.int64)
-    fg = np.stack([np.array([bin(int(x)).count("1") for x in gmask & ~g1]), np.array([bin(int(x)).count("1") for x in gmask & g1])], 1)
-    nkey = np.stack([U, smt, fg[:, 0], fg[:, 1], fc[:, 0], fc[:, 1]], 1)
-    ncls, ninv = np.unique(nkey, axis=0, return_inverse=True)
-    busy = (now - table.p4["busy_time"]) < O.MIN_BUSY_SECS
-    out = np.zeros((len(reqs), n), np.uint8)
-    memo = {}
-    for i, r in enumerate(reqs):
-        G = int(r["n_groups"])
-        gp = [int(x) for x in r["gpus"][:G]]
-        st = np.full(n, 6, np.uint8)
-
-        def verdicts(smt_c):
-            cpu = [int(x) for x in (r["cpu_smt"] if smt_c else r["cpu_nosmt"])[:G]] + [int(r["misc_smt"] if smt_c else r["misc_nosmt"])]
-            key = (tuple(gp), tuple(cpu))
-            if key not in memo:
-                gv, cv = np.zeros(len(ncls), bool), np.zeros(len(ncls), bool)
-                for k, (u, s, a0, a1, c0, c1) in enumerate(ncls.tolist()):
-                    for p in itertools.product(range(u), repeat=G):
-                        t = [0, 0]
-                        for g, x in zip(p, gp):
-                            t[g] += x
-                        gv[k] |= t[0] <= a0 and t[1] <= a1
-                    for p in itertools.product(range(u), repeat=G + 1):
-                        t = [0, 0]
-                        for g, x in zip(p, cpu):
-                            t[g] += x
-                        cv[k] |= t[0] <= c0 and t[1] <= c1
-                memo[key] = (gv, cv)
-            return memo[key]
-        for smt_c in (False, True):
-            gv, cv = verdicts(smt_c)
-            sel = smt == smt_c
-            st[sel & ~cv[ninv]] = 5
-            st[sel & ~gv[ninv]] = 4
-        if sum(gp):
-            st[busy] = 3
-        st[table.p2["hp_free"] < int(r["hugepages_gb"])] = 2
-        st[(flags & pack.NF_MAINTENANCE) != 0] = 1
-        if int(r["flags"]) & pack.RF_INITIAL_FILTER:
-            st[((flags & pack.NF_ACTIVE) == 0) | ((table.p3["groups"] & np.uint64(int(r["groups"]))) == 0)] = 0
-        out[i] = st
-    return out
 
 
 def _baseline(cfg, n, P):
@@ -110,7 +59,9 @@ def _baseline(cfg, n, P):
                          ids=["c4-65536x4096", "c5-shard", "c3-small", "c2-small"])
 def test_counts_against_the_verdict_bitmap(cfg, n, P):
     """Every pod's counts sum to the node count; FITS is the popcount of its column of nhdfit_find's bitmap; stages 0..5 equal the
-    host computation (and, at the small shapes, the per-node stages 6..8 are what is left over: not FITS, not 0..5)."""
+    host computation (and, at the small shapes, the per-node stages 6..8 are what is left over: not FITS, not 0..5).  At the small
+    shapes every count and every per-node stage also equals the C stage oracle's; the full-size shapes have their own test of that,
+    test_counts_equal_the_stage_oracle."""
     spec, table, reqs, eng = _baseline(cfg, n, P)
     now = spec.clock_now
     score, bm, _ = eng.find(reqs, now, want_map=False)
@@ -118,7 +69,7 @@ def test_counts_against_the_verdict_bitmap(cfg, n, P):
     assert counts.shape == (P, len(STAGES)) and (counts.sum(1) == n).all()
     feas = unpack_bitmap(bm, n)
     assert np.array_equal(counts[:, FITS], feas.sum(1))
-    host = host_stages_upto_cpu(table, reqs, now)
+    host = explain_check.host_stages_upto_cpu(table, reqs, now)
     for k in range(6):
         assert np.array_equal(counts[:, k], (host == k).sum(1)), k
     assert np.array_equal(counts[:, 6:].sum(1), (host == 6).sum(1))
@@ -126,7 +77,161 @@ def test_counts_against_the_verdict_bitmap(cfg, n, P):
         assert np.array_equal(stages == FITS, feas.astype(bool))
         assert np.array_equal(np.minimum(stages, 6), host)
         assert np.array_equal(counts, np.stack([(stages == k).sum(1) for k in range(len(STAGES))], 1))
+    if n * P <= 1 << 22:                 # the stage oracle on every pair (the full-size shapes: test_counts_equal_the_stage_oracle)
+        cl = coracle.Cluster.from_spec(spec)
+        want_c, want_s = cl.explain(oracle_pods(cl, cfg, P), now, per_node=True, threads=coracle.usable_cpus())
+        assert np.array_equal(counts, want_c)
+        assert np.array_equal(stages, want_s)
     eng.close()
+
+
+def oracle_pods(cl, cfg, P):
+    specs, groups = synth.make_pods(cfg, n_pods=P)
+    return cl.pods_from_tops([refmodel.make_topology(s) for s in specs], groups)
+
+
+def late_stages_seen(counts, which=LATE):
+    """Teeth: the inputs reach NIC, PCI and NUMA (`which`), so a swap of any two of them cannot pass."""
+    tot = np.asarray(counts).reshape(-1, len(STAGES)).sum(0)
+    assert (tot[which] > 0).all(), tot.tolist()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("cfg,n,P", [(4, 65536, 4096), (5, 32768, 2048)], ids=["c4-65536x4096", "c5-shard"])
+def test_counts_equal_the_stage_oracle(cfg, n, P):
+    """The full-size shapes of test_counts_against_the_verdict_bitmap: all ten count columns of every pod equal the C stage
+    oracle's (oracle_explain) over every one of the n x P pairs."""
+    if coracle.usable_cpus() < WHOLE_MATRIX_CPUS:
+        pytest.skip(f"fewer than {WHOLE_MATRIX_CPUS} usable CPUs: the whole-matrix stage oracle would take too long")
+    spec, table, reqs, eng = _baseline(cfg, n, P)
+    counts, _ = eng.explain(reqs, spec.clock_now)
+    eng.close()
+    cl = coracle.Cluster.from_spec(spec)
+    want, _ = cl.explain(oracle_pods(cl, cfg, P), spec.clock_now, threads=coracle.usable_cpus())
+    assert np.array_equal(counts, want)
+    late_stages_seen(counts, LATE if cfg == 4 else LATE[1:])        # (config 5's eight NICs per NUMA node never run short)
+
+
+def oracle_stages(nl, tops, now, groups=None, cand=None):
+    cl = coracle.Cluster.from_nodes(nl)
+    return cl.explain(cl.pods_from_tops(tops, groups), now, cand=cand, per_node=True, threads=coracle.usable_cpus())[1]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("occupancy", [0.3, 0.6])
+def test_random_clusters_stage_matrix_equals_the_oracle(occupancy):
+    """util.random_cluster (1- and 2-socket nodes, mixed NIC speeds and switches, maintenance, busy, inactive nodes) against
+    random NUMA / PCI / invalid pods of up to four groups, some of them with node groups: every (pod, node) stage is the oracle's."""
+    seed = 8300 + int(occupancy * 10)
+    nl = util.random_cluster(seed, 3000, occupancy=occupancy)
+    rng = np.random.default_rng(seed)
+    tops = [refmodel.make_topology(util.random_pod_spec(rng, max_groups=4)) for _ in range(300)]
+    groups = [None if rng.random() < 0.7 else list(rng.choice(["default", "alpha", "beta"], size=1)) for _ in tops]
+    m = HipMatcher(device=0, clock=lambda: util.CLOCK)
+    ex = m.ExplainNodes(nl, tops, pod_groups=groups, per_node=True)
+    assert all(e.error is None and e.unmirrored == 0 for e in ex)
+    got = np.stack([e.stages for e in ex])
+    want = oracle_stages(nl, tops, util.CLOCK, groups)
+    assert np.array_equal(got, want), np.argwhere(got != want)[:10].tolist()
+    late_stages_seen(np.stack([np.bincount(r, minlength=len(STAGES)) for r in want]))
+
+
+@pytest.mark.gpu
+def test_wide_nodes_stage_matrix_equals_the_oracle():
+    """util.mixed_cluster: 3- and 4-socket nodes and sockets of up to 128 cores (the wide records) among ordinary ones."""
+    nl = util.mixed_cluster(8400, 2500, wide_share=0.4)
+    rng = np.random.default_rng(8400)
+    tops = [refmodel.make_topology(util.random_pod_spec(rng, max_groups=4)) for _ in range(200)]
+    m = HipMatcher(device=0, clock=lambda: util.CLOCK)
+    ex = m.ExplainNodes(nl, tops, per_node=True)
+    assert all(e.error is None and e.unmirrored == 0 for e in ex)
+    assert sum(v.numa_nodes > 2 for v in nl.values()) > 100
+    got = np.stack([e.stages for e in ex])
+    want = oracle_stages(nl, tops, util.CLOCK)
+    assert np.array_equal(got, want), np.argwhere(got != want)[:10].tolist()
+    late_stages_seen(np.stack([np.bincount(r, minlength=len(STAGES)) for r in want]))
+
+
+@pytest.mark.gpu
+def test_big_pods_stage_matrix_equals_the_oracle():
+    """Pods of 5..8 processing groups (nhdfit_explain_big) on a c4-shaped cluster of 4 000 nodes.  A pod the device returns with
+    `error` set (its NIC search beyond the budget) is left out and counted; such pods must stay a small minority."""
+    spec = synth.make_cluster(4, n_nodes=4000)
+    nl = spec.build_nodes()
+    rng = np.random.default_rng(8500)
+    tops = [refmodel.make_topology(big_spec(rng, 5, 8)) for _ in range(32)]
+    assert all(pack.needs_general_path(t) for t in tops)
+    m = HipMatcher(device=0, clock=lambda: spec.clock_now)
+    ex = m.ExplainNodes(nl, tops, per_node=True)
+    ok = [i for i, e in enumerate(ex) if e.error is None]
+    assert len(ok) >= 0.8 * len(tops), [e.error for e in ex if e.error is not None]
+    assert all(ex[i].unmirrored == 0 for i in ok)
+    got = np.stack([ex[i].stages for i in ok])
+    want = oracle_stages(nl, [tops[i] for i in ok], spec.clock_now)
+    assert np.array_equal(got, want), np.argwhere(got != want)[:10].tolist()
+    late_stages_seen(np.stack([np.bincount(r, minlength=len(STAGES)) for r in want]))
+
+
+def mask_words(keep, extra_high_bits=False):
+    """n booleans -> the uint64 words nhdfit_explain takes; `extra_high_bits` sets every bit of the last word past n."""
+    n = len(keep)
+    bits = np.zeros(((n + 63) // 64) * 64, bool)
+    bits[:n] = keep
+    if extra_high_bits:
+        bits[n:] = True
+    return np.ascontiguousarray(np.packbits(bits.reshape(-1, 64), axis=1, bitorder="little").view("<u8").reshape(-1))
+
+
+@pytest.mark.gpu
+def test_candidate_masks_against_the_oracle():
+    """Random candidate masks on 3 001 nodes (not a multiple of 64): outside the mask the stage is NOT_CANDIDATE, inside it is
+    the oracle's; bits set in the last word past the node count change nothing."""
+    cfg, n, P = 4, 3001, 256
+    spec, table, reqs, eng = _baseline(cfg, n, P)
+    now = spec.clock_now
+    cl = coracle.Cluster.from_spec(spec)
+    pods = oracle_pods(cl, cfg, P)
+    rng = np.random.default_rng(8600)
+    seen = np.zeros(len(STAGES), np.int64)
+    for share in (0.9, 0.5, 0.05):
+        keep = rng.random(n) < share
+        counts, stages = eng.explain(reqs, now, cand=mask_words(keep), per_node=True)
+        want_c, want_s = cl.explain(pods, now, cand=keep, per_node=True, threads=coracle.usable_cpus())
+        assert (stages[:, ~keep] == 0).all()
+        assert np.array_equal(stages, want_s) and np.array_equal(counts, want_c)
+        c2, s2 = eng.explain(reqs, now, cand=mask_words(keep, extra_high_bits=True), per_node=True)
+        assert np.array_equal(c2, counts) and np.array_equal(s2, stages)
+        seen += counts.sum(0).astype(np.int64)
+    late_stages_seen(seen)
+    eng.close()
+
+
+@pytest.mark.gpu
+def test_three_shards_on_one_device_against_the_oracle():
+    """GroupEngine over three contexts on device 0 (as test_mode_b_across_shards_on_the_device builds it) on 2 001 nodes: the
+    stages, put together in global node order, and the summed counts equal the oracle's, with and without a candidate mask."""
+    cfg, n, P = 4, 2001, 200
+    spec = synth.make_cluster(cfg, n_nodes=n)
+    specs, groups = synth.make_pods(cfg, n_pods=P)
+    tops = [refmodel.make_topology(s) for s in specs]
+    pk = pack.Packer()
+    table = planes.planes_from_spec(pk, spec)
+    reqs = pk.digest_many(tops, groups)
+    grp = GroupEngine([0, 0, 0], engine_factory=Engine)
+    grp.set_dictionary(pk)
+    grp.upload(table)
+    assert len([1 for lo, hi in grp._bounds if hi > lo]) == 3
+    cl = coracle.Cluster.from_spec(spec)
+    pods = cl.pods_from_tops(tops, groups)
+    keep = np.random.default_rng(8700).random(n) < 0.7
+    seen = np.zeros(len(STAGES), np.int64)
+    for cand in (None, keep):
+        counts, stages = grp.explain(reqs, spec.clock_now, cand=None if cand is None else mask_words(cand), per_node=True)
+        want_c, want_s = cl.explain(pods, spec.clock_now, cand=cand, per_node=True, threads=coracle.usable_cpus())
+        assert np.array_equal(stages, want_s) and np.array_equal(counts, want_c)
+        seen += counts.sum(0).astype(np.int64)
+    late_stages_seen(seen)
+    grp.close()
 
 
 @pytest.mark.gpu
