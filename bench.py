@@ -5,6 +5,12 @@
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W
 
+A plain run does what the headline needs and no more: set up, the cold-start region, settle, the headline region,
+--dump-outputs, one JSON line.  `--full` adds everything else the line can carry, each after the headline region: the
+repeats of the timed region and the steady state, the in-run rocprofv3 counter passes, the extra legs (end to end, single
+and big-pod finds, mode B with its oracle parity, the other BASELINE shapes, deltas, the scheduler loop, score only), the
+CPU baseline and, at N > 1, BASELINE's strong-scaling legs.  --no-pmc / --no-extras / --no-cpu-baseline thin out --full.
+
 One step = one pass of the whole path over one batch of pending pods with the cluster mirror and the
 request records already resident in HBM: request digest -> fit+score over every (pod, node) pair of
 this rank's node shard -> [RCCL all-reduce(max) of the packed scores] -> winner mapping.  The library issues
@@ -53,10 +59,12 @@ def main():
     ap.add_argument("--nodes-per-gpu", type=int, default=65536)
     ap.add_argument("--total-nodes", type=int, default=0, help="strong scaling: fixed cluster size, shards of total/N nodes")
     ap.add_argument("--pods", type=int, default=4096)
-    ap.add_argument("--cpu-sample-pods", type=int, default=1024, help="pods timed on the CPU port (rank 0, N=1 only)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the in-run rocprofv3 counter passes (HBM traffic of the step kernel)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the mode-B and end-to-end legs after the timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: repeats, steady state, counter passes, extra legs, CPU baseline, strong-scaling legs (N > 1)")
+    ap.add_argument("--cpu-sample-pods", type=int, default=1024, help="pods timed on the CPU port (--full, rank 0, N=1 only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-pmc", action="store_true", help="with --full: skip the in-run rocprofv3 counter passes (HBM traffic of the step kernel)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the mode-B, end-to-end and other-shape legs after the timed region")
     ap.add_argument("--settle-ms", type=float, default=30.0, help="how long the device is kept busy with the benchmarked step in front of the headline region")
     ap.add_argument("--settle-regions", type=int, default=0, help="experiment: untimed W + K regions (each closed by a sync) at the end of the settling phase")
     ap.add_argument("--no-settle", action="store_true", help="time the W + K steps as the first GPU work of the process only (no clock settling in front of the headline region)")
@@ -140,9 +148,12 @@ def main():
     # `value`: the same W + K steps after the device has been kept busy with this very step for >= 30 ms (`settle`) - the
     # state a scheduler that runs all day is in.  Nothing is skipped or cached in either: every step is digest + fit +
     # mapping with the verdict matrix written.
+    # (NHD_BENCH_INNER: a counter pass of measure_counters - the W + K steps as the process's first GPU work, nothing else)
+    inner = bool(os.environ.get("NHD_BENCH_INNER"))
+    full = args.full and not inner
     cold = None
     settled = 0
-    if not os.environ.get("NHD_BENCH_INNER") and not args.no_settle:
+    if not inner and not args.no_settle:
         cold = timed_region()
         settled = settle(eng, now, settle_ms=args.settle_ms, fixed_steps=2500 if world > 1 else 0)
         for _ in range(args.settle_regions):
@@ -162,9 +173,9 @@ def main():
         dt = float(t.item())
 
     st = eng.stats()
-    # the timed region again, five times (same K steps, same barriers): spread of the headline figure
+    # --full: the timed region again, five times (same K steps, same barriers): spread of the headline figure
     rep = []
-    for _ in range(5 if not os.environ.get("NHD_BENCH_INNER") else 0):
+    for _ in range(5 if full else 0):
         barrier()
         eng.sync()
         r0 = time.perf_counter()
@@ -173,7 +184,7 @@ def main():
         eng.sync()
         barrier()
         rep.append((time.perf_counter() - r0) * 1e3 / args.steps)
-    steady = steady_state(eng, now, barrier, args.pods, n_total, fixed_steps=2500 if world > 1 else 0) if not os.environ.get("NHD_BENCH_INNER") else None
+    steady = steady_state(eng, now, barrier, args.pods, n_total, fixed_steps=2500 if world > 1 else 0) if full else None
     score, _, maps = eng.fetch(want_bitmap=False, want_map=True)
     evals = float(args.pods) * n_total * args.steps
     ms_per_step = dt * 1e3 / args.steps
@@ -182,13 +193,12 @@ def main():
     # then overlaps its neighbour's, and the rate at which k_step moves bytes is pipes x (bytes per launch) / duration
     pipes = max(1, int(getattr(st, "pipes", 1) or 1))
     achieved = pipes * st.bytes_last / (fit_ms * 1e-3) / 1e9 if fit_ms > 0 else 0.0
-    inner = bool(os.environ.get("NHD_BENCH_INNER"))
 
-    # HBM traffic of the step kernel from hardware counters: short rocprofv3 passes of this very script (FETCH_SIZE,
+    # HBM traffic of the step kernel from hardware counters (--full): short rocprofv3 passes of this very script (FETCH_SIZE,
     # WRITE_SIZE, SQ_INSTS_VALU; one counter set per pass, never combined with tracing), rank 0 at N = 1.  Falls back
     # to the committed profile of the same workload, and says which of the two it is.
     counters = None
-    if rank == 0 and world == 1 and not args.no_pmc and not inner:
+    if full and rank == 0 and world == 1 and not args.no_pmc:
         counters = measure_counters(args)
     traffic, traffic_source = None, None
     if counters and counters.get("hbm_bytes_per_launch"):
@@ -210,7 +220,7 @@ def main():
         "value": evals / dt, "unit": "evals/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "strong" if strong else "weak", "vs_baseline": None,
         "dtype": "u64 bitmaps + int32 table look-ups (f64 NIC arithmetic in the request digest)", "data": "synthetic",
-        "snapshot_decisions_per_s": args.pods * args.steps / dt,
+        "snapshot_decisions_per_s": args.pods * args.steps / dt, "full": full,
         "repeats": None if not rep else {"n": len(rep), "ms_per_step_min": min(rep), "ms_per_step_median": sorted(rep)[len(rep) // 2],
                                          "ms_per_step_max": max(rep), "note": "the timed region repeated after the headline measurement (rank-local clock)"},
         "steady_state": steady,
@@ -230,7 +240,7 @@ def main():
         "roofline": roofline(st, fit_ms, achieved, traffic, traffic_source, valu, counters, pipes, ms_per_step),
     }
 
-    if rank == 0 and world == 1 and not args.no_extras and not inner:
+    if full and rank == 0 and world == 1 and not args.no_extras:
         out["end_to_end"] = end_to_end(eng, reqs, now, args.pods, n_total)
         out["single_find"] = single_find(eng, reqs, now, n_total)
         out["mode_b"] = mode_b(eng, pk, reqs, now, args.pods, parity=(spec, tops, pod_groups))
@@ -239,9 +249,9 @@ def main():
         out["big_pod_find"] = big_pod_find(eng, pk, pods, pod_groups, tops, reqs, now, n_total)
         out["sched_loop"] = sched_loop(args.config, local_rank)
         out["score_only"] = score_only(eng, reqs, now, args.pods, n_total)     # last: it changes the context's outputs
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not inner:
+    if full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(spec, tops, pod_groups, args.cpu_sample_pods, score, lo, winner_index, args)
-    if world > 1 and not strong and not args.no_extras:
+    if full and world > 1 and not strong and not args.no_extras:
         # BASELINE.json's own multi-GPU shapes ride along (strong scaling: the cluster is fixed, the shards shrink), so that one
         # run per N yields both curves: config 4's 65 536 nodes x 4 096 pods at every N, config 5's 262 144 x 16 384 at N = 8
         legs = [(4, 65536, 4096)] + ([(5, 262144, 16384)] if world == 8 else [])
@@ -795,12 +805,13 @@ def mode_b_parity(spec, tops, pod_groups, now, reqs, node, maps, places, status)
 
 
 def measure_counters(args):
-    """HBM bytes and VALU instructions per k_step launch: this script under rocprofv3, one counter set per pass."""
+    """HBM bytes and VALU instructions per k_step launch: this script under rocprofv3 (a plain run of the same workload), one counter
+    set per pass."""
     rocprof = shutil.which("rocprofv3")
     if not rocprof:
         return None
     base = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", "60", "--warmup", "5", "--config", str(args.config),
-            "--nodes-per-gpu", str(args.nodes_per_gpu), "--pods", str(args.pods), "--no-cpu-baseline", "--no-pmc", "--no-extras"]
+            "--nodes-per-gpu", str(args.nodes_per_gpu), "--pods", str(args.pods)]
     env = dict(os.environ, NHD_BENCH_INNER="1", TMPDIR="/tmp")
     got = {}
     tmp = tempfile.mkdtemp(prefix="nhdbench_", dir="/tmp")

@@ -43,10 +43,14 @@ runpy.run_path({bench!r}, run_name="__main__")
 """
 
 
+_FULL_SCRIPT = _SINGLE_SCRIPT.replace('"--no-pmc"]', '"--no-pmc", "--full"]')
+
+
 def test_bench_json_contract(tmp_path):
+    """`--full`: every leg behind the headline runs, with its in-run parity asserts."""
     import subprocess
     script = tmp_path / "single.py"
-    script.write_text(_SINGLE_SCRIPT.format(root=ROOT, bench=os.path.join(ROOT, "bench.py")))
+    script.write_text(_FULL_SCRIPT.format(root=ROOT, bench=os.path.join(ROOT, "bench.py")))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     res = subprocess.run([sys.executable, str(script)], env=env, capture_output=True, text=True, timeout=300)
     assert res.returncode == 0, res.stderr
@@ -103,14 +107,17 @@ runpy.run_path({bench!r}, run_name="__main__")
 """
 
 
+_RANK_FULL_SCRIPT = _RANK_SCRIPT.replace('"--pods", "40"]', '"--pods", "40", "--full"]')
+
+
 def test_bench_two_ranks_control_plane(tmp_path):
-    """`--gpus 2` as the driver launches it (one process per rank, RANK / WORLD_SIZE / MASTER_* in the env, gloo
-    control plane): rank 0 prints the one JSON line with n_gpus = 2 and both shards' nodes, rank 1 prints nothing."""
+    """`--gpus 2 --full` as torch.distributed.run launches it (one process per rank, RANK / WORLD_SIZE / MASTER_* in the env,
+    gloo control plane): rank 0 prints the one JSON line with n_gpus = 2 and both shards' nodes, rank 1 prints nothing."""
     import socket
     import subprocess
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
     script = tmp_path / "rank.py"
-    script.write_text(_RANK_SCRIPT.format(root=ROOT, bench=os.path.join(ROOT, "bench.py")))
+    script.write_text(_RANK_FULL_SCRIPT.format(root=ROOT, bench=os.path.join(ROOT, "bench.py")))
     procs = []
     for rank in range(2):
         env = dict(os.environ, RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE="2", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
@@ -200,3 +207,58 @@ def test_bench_dump_outputs(tmp_path):
     score = (a["score_hi.npy"].astype(np.uint64) << np.uint64(32)) | a["score_lo.npy"].astype(np.uint64)
     assert score.shape == (96,) and np.count_nonzero(score) > 0 and np.count_nonzero(a["map_valid.npy"]) > 0
     assert a["bitmap_hi.npy"].shape == (16, 96) and np.array_equal(a["bitmap_pods.npy"], np.arange(96))
+
+
+_PLAIN_SCRIPT = r"""
+import runpy, subprocess, sys
+sys.path.insert(0, {root!r})
+from tests.test_bench_dryrun import DryEngine
+import nhd_amd.engine as eng_mod
+eng_mod.Engine = DryEngine
+# what a plain run must not do: start a process (the rocprofv3 counter passes), generate another shape (the other_configs /
+# sched_loop legs), import the oracle (the parity checks and the CPU baseline)
+children, shapes = [], []
+def _child(*a, **k):
+    children.append(a)
+    raise OSError("no child processes in a plain run")
+subprocess.run = subprocess.Popen = _child
+from workload import synth
+_mc = synth.make_cluster
+def _cluster(cfg, n_nodes=None, **kw):
+    shapes.append((cfg, n_nodes))
+    return _mc(cfg, n_nodes=n_nodes, **kw)
+synth.make_cluster = _cluster
+before = set(sys.modules)
+sys.argv = ["bench.py", "--steps", "3", "--warmup", "1", "--nodes-per-gpu", "1024", "--pods", "96", "--dump-outputs", sys.argv[1]]
+runpy.run_path({bench!r}, run_name="__main__")
+assert not children, children
+assert shapes == [(4, 1024)], shapes
+assert not [m for m in set(sys.modules) - before if m.split(".")[0] == "oracle"]
+"""
+
+
+def test_bench_plain_run_is_lean(tmp_path):
+    """Without --full the run sets up, times the headline, dumps and prints its line - nothing else: no counter pass, no other
+    shape, no oracle, none of the keys that only --full fills; the dump is the one the plain run has always written."""
+    import subprocess
+    import numpy as np
+    script = tmp_path / "plain.py"
+    script.write_text(_PLAIN_SCRIPT.format(root=ROOT, bench=os.path.join(ROOT, "bench.py")))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "NHD_BENCH_INNER")}
+    res = subprocess.run([sys.executable, str(script), str(tmp_path / "dump")], env=env, capture_output=True, text=True, timeout=300)
+    assert res.returncode == 0, res.stderr
+    lines = [ln for ln in res.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1
+    out = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup", "config", "roofline",
+                "cold_start", "protocol", "placed_pods"):
+        assert key in out, key
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["unit"] == "evals/s" and out["higher_is_better"] is True
+    assert out["value"] > 0 and out["ms_per_step"] > 0 and out["cold_start"] is not None and out["full"] is False
+    assert out["repeats"] is None and out["steady_state"] is None
+    for key in ("end_to_end", "single_find", "mode_b", "other_configs", "deltas", "big_pod_find", "sched_loop", "score_only",
+                "cpu_baseline", "strong_scaling"):
+        assert key not in out, key
+    assert not out["roofline"]["traffic_source"] or not out["roofline"]["traffic_source"].startswith("measured in this run")
+    assert {"score_hi.npy", "score_lo.npy", "bitmap_hi.npy", "bitmap_lo.npy", "bitmap_pods.npy", "map_valid.npy"} <= {p.name for p in (tmp_path / "dump").iterdir()}
+    assert np.count_nonzero(np.load(tmp_path / "dump" / "score_lo.npy")) > 0

@@ -8,7 +8,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-BENCH="python $ROOT/bench.py --steps 100 --warmup 5 --no-cpu-baseline $*"   # >= 100 steps: the few digest-only / flush launches of k_step must not dilute the per-launch means
+BENCH="python $ROOT/bench.py --full --steps 100 --warmup 5 --no-cpu-baseline $*"   # >= 100 steps: the few digest-only / flush launches of k_step must not dilute the per-launch means
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o s -- $BENCH > $OUT/stats.log 2>&1
 i=0
 # QUICK=1: only the instruction-mix pass and the two HBM-traffic passes

@@ -5,7 +5,7 @@
 #   2. one rank per GPU, a communicator, the ring's rank-to-rank exchange (nhdfit_comm_sendrecv) and the uint8 sum on 2 ranks;
 #   3. mode A over 2 shards: the all-reduce(max) of the packed scores gives the single-GPU winners (small cluster, oracle-checked);
 #   4. mode B over 2 shards (nhd_amd.sharding.schedule_batch_sharded over RcclTransport) against the oracle's loop;
-#   5. bench.py --gpus N for N in 2 4 8 (as the driver launches it).
+#   5. bench.py --full --gpus N for N in 2 4 8 (the headline and BASELINE's strong-scaling legs with their mode-B parity).
 #   bash tools/scale_first_run.sh [max_gpus]
 set -u
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
@@ -68,8 +68,8 @@ PY
 NHD_ROOT=$ROOT run 2 /tmp/nhd_scale_step.py || { echo "steps 2-4 failed on 2 ranks: see the traceback above (RCCL banner: NCCL_DEBUG=INFO)"; exit 1; }
 for n in 2 4 8; do
   [ $n -le $MAXG ] || break
-  echo "step 5: bench.py --gpus $n"
-  run $n bench.py --gpus $n --steps 20 --warmup 5 | tail -n 1 | python -c "
+  echo "step 5: bench.py --full --gpus $n"
+  run $n bench.py --full --gpus $n --steps 20 --warmup 5 | tail -n 1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.readline()); print('  n_gpus', d['n_gpus'], 'evals/s %.3g' % d['value'], 'ms/step %.4f' % d['ms_per_step'], 'strong', [(l.get('config'), l.get('ms_per_step'), (l.get('mode_b') or {}).get('decisions_per_s'), ((l.get('mode_b') or {}).get('parity') or {}).get('identical'), (l.get('mode_b') or {}).get('error')) for l in d.get('strong_scaling', [])])" || { echo "bench.py --gpus $n failed"; exit 1; }
 done
