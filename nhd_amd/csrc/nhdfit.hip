@@ -36,6 +36,7 @@
 #include "wide_core.h"
 #include "explain_core.h"
 #include "dict_stream.h"
+#include "host_streams.h"
 
 using namespace nhdfit;
 
@@ -138,10 +139,9 @@ constexpr int kEventRing = 256;
 constexpr int kBufs = 8;          // buffer sets: step s owns set s % kBufs from its digest (one launch before its fit)
                                   // to the end of its mapping (four launches after it, five when sharded)
 
-constexpr int kPipes = 3;           // pipelines a context owns; a staged batch deals its steps to two of them, or to all three (nhdfit_enqueue_step)
-struct Pipe {                            // one software pipeline of steps: its stream, its buffer sets, how far each phase got
-    hipStream_t stream = nullptr;
-    hipEvent_t ev_fit[kBufs] = {}, ev_red[kBufs] = {};   // stream <-> s_red hand-over (sharded runs only)
+struct Pipe {                            // one software pipeline of steps: its buffer sets, how far each phase got
+    int k = 0;                           // its index - and its stream's in the context's ledger (host_streams.h)
+    hipEvent_t ev_fit[kBufs] = {}, ev_red[kBufs] = {};   // pipe's stream <-> reduce stream hand-over (sharded runs only)
     hipEvent_t ev_staged = nullptr;      // pipe 0 records it behind what it staged (requests, work items, node records); pipe 1 waits for it
     uint64_t n_dig = 0, n_fit = 0, n_shaped = 0, n_chosen = 0, n_finished = 0;   // steps (since the last stage_requests) whose phase was launched
     uint64_t seen_gen = 0;               // the staging generation of pipe 0's stream this pipe has waited for (nhdfit_ctx::staged_gen)
@@ -160,14 +160,11 @@ struct nhdfit_ctx {
     // Several pipes: the pipelined form (stage, enqueue, enqueue, ...) deals its steps round robin to independent software
     // pipelines on their own streams, so that one step's launch gap, table staging and tail are covered by the other steps'
     // blocks (two against one: 23 -> 17 us per step, profiles/r03; a third where the digest is a long chain, profiles/r04).
-    // Everything else - single finds, mode B, uploads, deltas - runs on pipe 0, whose stream is `stream`; whatever changes the
-    // mirror waits for all of them (sync_all).
+    // Everything else - single finds, mode B, uploads, deltas - runs on pipe 0; whatever changes the mirror waits for every
+    // stream that may hold work (sync_all).
     Pipe pipe[kPipes];
-    hipStream_t stream = nullptr;        // = pipe[0].stream: uploads, deltas, commits, mode B, single finds
-    hipStream_t s_red = nullptr;         // the all-reduce of sharded runs, overlapping the next step launch
-    bool side_streams_used = true;       // something was enqueued on a pipe other than the first, or on s_red, since sync_all last waited for them
+    StreamLedger streams;                // stream k = pipe k's, kRed = the reduce stream's; use(k) hands out a handle and marks the stream
     double enq_us = 0, enq_launch_us = 0, enq_events_us = 0; uint64_t enq_n = 0;   // tuning aid (NHDFIT_ENQ_PROF): host time of nhdfit_enqueue_step, of the launch calls, of the event records
-    bool known_idle = false;             // no HIP call of this context since its streams were last seen idle (sync_all; a single-launch find's polled word)
     bool dual = tune_env("NHDFIT_ONE_PIPE") == nullptr;   // tuning aid: NHDFIT_ONE_PIPE=1 keeps every step on pipe 0
     uint64_t n_enq = 0;                  // steps enqueued since the last stage_requests (step k runs on pipe k % 2)
     int last_pipe = 0;                   // the pipe of the most recent step (nhdfit_fetch reads its results)
@@ -320,38 +317,41 @@ int fail(nhdfit_ctx* c, int code, const char* fmt, ...) {
 
 #define HIPCHK(c, expr)                                                                         \
     do {                                                                                        \
-        (c)->known_idle = false;          /* (whatever it is, it may put work on a stream) */   \
         hipError_t e_ = (expr);                                                                 \
         if (e_ != hipSuccess) return fail((c), NHDFIT_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
-
-// Everything that puts work on a stream clears known_idle in one place: the HIP calls through HIPCHK above, the kernel launches through
-// LAUNCH, the collectives through the comma form at their call sites (`(c->known_idle = false, g_rccl).AllReduce(...)`) - the
-// idle shortcut of stage_requests must never see a stale `true`.
-#define LAUNCH(c, ...)                                   \
+#define TRY(expr)                                        \
     do {                                                 \
-        (c)->known_idle = false;                         \
-        hipLaunchKernelGGL(__VA_ARGS__);                 \
+        const int rc_ = (expr);                          \
+        if (rc_) return rc_;                             \
     } while (0)
 
-// Waiting for a stream: the runtime's own wait parks the thread on the queue's interrupt, and the wake-up costs tens of
-// microseconds - as much as a whole step of the pipelined form, half of what a 20-step region loses at its end, a third of a
-// batch call through host buffers.  The scheduler's thread has nothing else to do while its one call is in flight (the reference
-// calls FindNode from one thread, nhd/NHDScheduler.py:43,277), so it polls the stream first - for at most kSpinWaitUs, the length of
-// the longest ordinary call (a mode-B batch) - and only then goes to sleep on it.
-constexpr long kSpinWaitUs = 20000;
-hipError_t wait_stream(hipStream_t s) {
-    const auto t0 = std::chrono::steady_clock::now();
-    for (uint32_t polls = 0;; ++polls) {
-        const hipError_t e = hipStreamQuery(s);
-        if (e != hipErrorNotReady) {
-            if (polls && e == hipSuccess) (void)hipGetLastError();      // ("not ready" must not be what the next launch's error check finds)
-            return e;
+// Whatever puts work on a stream - launch, async copy or fill, event record, wait for an event, collective - takes the handle from
+// c->streams.use(k), which marks stream k; c->streams.wait(k) clears the mark (host_streams.h).  The shortcuts that skip a wait
+// (sync_all, stage_requests, nhdfit_commit) read those marks and nothing else.
+
+// A collective on stream k: the handle from the ledger, the error worded here.
+template <class Fn, class... Args>
+int rccl(nhdfit_ctx* c, int k, const char* what, Fn Rccl::*fn, Args... args) {
+    const ncclResult_t r = (g_rccl.*fn)(args..., c->streams.use(k));
+    return r == ncclSuccess ? NHDFIT_OK : fail(c, NHDFIT_E_RCCL, "%s: %s", what, g_rccl.GetErrorString(r));
+}
+
+// The single-launch calls get their results in fine-grained host memory, behind a word the launch stores last: the host polls it, and
+// after budget_us - a long launch, or host memory the device does not write through - waits for stream k instead.  `seen`: the word
+// as last read (`want`, `or_else`, or after the wait whatever it holds).
+int poll_word(nhdfit_ctx* c, const uint32_t* word, uint32_t want, uint32_t or_else, std::chrono::steady_clock::time_point t_launch,
+              long budget_us, int k, uint32_t& seen) {
+    for (uint32_t spins = 1;; ++spins) {
+        seen = __atomic_load_n(word, __ATOMIC_ACQUIRE);
+        if (seen == want || seen == or_else) return NHDFIT_OK;
+        if ((spins & 255u) == 0 && std::chrono::steady_clock::now() - t_launch > std::chrono::microseconds(budget_us)) {
+            HIPCHK(c, c->streams.wait(k));
+            seen = __atomic_load_n(word, __ATOMIC_ACQUIRE);
+            return NHDFIT_OK;
         }
-        if ((polls & 63u) == 63u && std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count() > kSpinWaitUs) break;
+        __builtin_ia32_pause();
     }
-    (void)hipGetLastError();
-    return hipStreamSynchronize(s);
 }
 
 int drain_events(nhdfit_ctx* c) {
@@ -373,16 +373,28 @@ constexpr size_t kLdsPerCu = 160 * 1024;      // gfx950
 int flush_pipeline(nhdfit_ctx* c);
 int refresh_layouts(nhdfit_ctx* c);
 
+// Tuning build only: where a shortcut skips the wait for a pipe other than the first or for the reduce stream because the ledger holds
+// no mark for it, the runtime is asked after all, and the call fails if the stream is not idle - every run of the GPU tests against
+// libnhdfit_tuning.so is a test of the ledger.  (Pipe 0 is exempt: behind a polled word its last launch may still be retiring.)
+int check_skipped_waits(nhdfit_ctx* c, const char* entry) {
+#ifdef NHDFIT_TUNING
+    for (int k = 1; k < kStreams; ++k)
+        if (c->streams.clean(k) && c->streams.query(k) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(c, NHDFIT_E_STATE, "%s skipped the wait for %s, which the ledger holds clean and the runtime does not", entry,
+                        k == kRed ? "the reduce stream" : k == 1 ? "the stream of pipe 1" : "the stream of pipe 2");
+        }
+#endif
+    return NHDFIT_OK;
+}
+
 int sync_all(nhdfit_ctx* c) {
-    { int rc_ = flush_pipeline(c); if (rc_) return rc_; }      // pending mapping phases of the last steps
-    // the other pipes' streams and the reduce stream only ever carry the steps of a staged batch (launch_step, flush_pipeline) and calls
-    // that wait for their own work: nothing was put on them since the last wait here -> nothing to ask (a query of an idle stream is ~3 us,
+    TRY(flush_pipeline(c));      // pending mapping phases of the last steps
+    // a stream without a mark has carried nothing since it was last waited for -> nothing to ask (a query of an idle stream is ~3 us,
     // four of them were a tenth of a small nhdfit_find)
-    for (Pipe& p : c->pipe)
-        if (&p == &c->pipe[0] || c->side_streams_used) HIPCHK(c, wait_stream(p.stream));
-    if (c->side_streams_used) HIPCHK(c, wait_stream(c->s_red));
-    c->side_streams_used = false;
-    c->known_idle = true;
+    TRY(check_skipped_waits(c, "sync_all"));
+    for (int k = 0; k < kStreams; ++k)
+        if (!c->streams.clean(k)) HIPCHK(c, c->streams.wait(k));
     return NHDFIT_OK;
 }
 
@@ -425,16 +437,15 @@ int nhdfit_create(int device_id, nhdfit_ctx** out) {
         delete c;
         return rc;
     }
-    e = hipStreamCreateWithFlags(&c->s_red, hipStreamNonBlocking);
+    e = c->streams.create();
     for (Pipe& p : c->pipe) {
-        if (e == hipSuccess) e = hipStreamCreateWithFlags(&p.stream, hipStreamNonBlocking);
+        p.k = (int)(&p - c->pipe);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&p.ev_staged, hipEventDisableTiming);
         for (int b = 0; b < kBufs && e == hipSuccess; ++b) {
             e = hipEventCreateWithFlags(&p.ev_fit[b], hipEventDisableTiming);
             if (e == hipSuccess) e = hipEventCreateWithFlags(&p.ev_red[b], hipEventDisableTiming);
         }
     }
-    c->stream = c->pipe[0].stream;
     for (auto& q : c->ev)
         for (auto& x : q)
             if (e == hipSuccess) e = hipEventCreate(&x);
@@ -443,17 +454,17 @@ int nhdfit_create(int device_id, nhdfit_ctx** out) {
     if (e == hipSuccess) e = hipHostMalloc((void**)&c->commit_host, sizeof(CommitHost), hipHostMallocCoherent);
     if (e == hipSuccess) memset(c->commit_host, 0, sizeof(CommitHost));
     if (e == hipSuccess) e = c->find_sync.reserve(8);                  // [0..2] counters of k_find / k_find1, [4..5] k_find1's 64-bit score word
-    if (e == hipSuccess) e = hipMemsetAsync(c->find_sync.p, 0, 8 * sizeof(uint32_t), c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(c->find_sync.p, 0, 8 * sizeof(uint32_t), c->streams.use(0));
     if (e == hipSuccess) e = c->xkeys.reserve(kXSlots);
     if (e == hipSuccess) e = c->xids.reserve(kXSlots);
     if (e == hipSuccess) e = c->xcls.reserve(kXSlots / 2);
     if (e == hipSuccess) e = c->xnx.reserve(2);
-    if (e == hipSuccess) e = hipMemsetAsync(c->xkeys.p, 0, kXSlots * sizeof(unsigned long long), c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(c->xids.p, 0xFF, kXSlots * sizeof(uint32_t), c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(c->xnx.p, 0, 2 * sizeof(uint32_t), c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(c->xkeys.p, 0, kXSlots * sizeof(unsigned long long), c->streams.use(0));
+    if (e == hipSuccess) e = hipMemsetAsync(c->xids.p, 0xFF, kXSlots * sizeof(uint32_t), c->streams.use(0));
+    if (e == hipSuccess) e = hipMemsetAsync(c->xnx.p, 0, 2 * sizeof(uint32_t), c->streams.use(0));
     if (e == hipSuccess) e = c->asc.reserve(kAscEntries);
     if (e == hipSuccess) {
-        LAUNCH(c, k_build_asc, dim3((kAscEntries + 255) / 256), dim3(256), 0, c->stream, c->asc.p);
+        hipLaunchKernelGGL(k_build_asc, dim3((kAscEntries + 255) / 256), dim3(256), 0, c->streams.use(0), c->asc.p);
         e = hipGetLastError();
         if (e == hipSuccess && c->use_set_states) {
             std::vector<uint64_t> info;
@@ -469,10 +480,10 @@ int nhdfit_create(int device_id, nhdfit_ctx** out) {
         }
         if (e == hipSuccess) e = c->choose_tab.reserve(kChooseEntries);
         if (e == hipSuccess) {
-            LAUNCH(c, k_build_choose, dim3((kChooseEntries + 255) / 256), dim3(256), 0, c->stream, c->asc.p, c->choose_tab.p);
+            hipLaunchKernelGGL(k_build_choose, dim3((kChooseEntries + 255) / 256), dim3(256), 0, c->streams.use(0), c->asc.p, c->choose_tab.p);
             e = hipGetLastError();
         }
-        if (e == hipSuccess) e = wait_stream(c->stream);
+        if (e == hipSuccess) e = c->streams.wait(0);         // (a fresh context starts with every stream clean)
     }
     if (e != hipSuccess) {
         int rc = fail(nullptr, NHDFIT_E_HIP, "stream / event / table creation: %s", hipGetErrorString(e));
@@ -514,12 +525,11 @@ void nhdfit_destroy(nhdfit_ctx* c) {
             if (p.ev_red[b]) (void)hipEventDestroy(p.ev_red[b]);
         }
         if (p.ev_staged) (void)hipEventDestroy(p.ev_staged);
-        if (p.stream) (void)hipStreamDestroy(p.stream);
     }
     for (auto& q : c->ev)
         for (auto& x : q)
             if (x) (void)hipEventDestroy(x);
-    if (c->s_red) (void)hipStreamDestroy(c->s_red);
+    c->streams.destroy();
     delete c;
 }
 
@@ -543,7 +553,7 @@ int nhdfit_set_dictionary(nhdfit_ctx* c, uint32_t max_cores_per_numa, uint32_t m
     if (n_group_sets && !group_sets) return fail(c, NHDFIT_E_INVAL, "NULL group set table");
     if (nsig > 0xFFFF) return fail(c, NHDFIT_E_LIMIT, "%u NIC signatures (max 65535)", nsig);
     HIPCHK(c, hipSetDevice(c->dev));
-    { int rc_ = sync_all(c); if (rc_) return rc_; }
+    TRY(sync_all(c));
     c->rec_all = true;                                  // node records depend on the mirror and on the table layout
     HIPCHK(c, c->group_sets.reserve(n_group_sets ? n_group_sets : 1));
     if (n_group_sets) HIPCHK(c, hipMemcpy(c->group_sets.p, group_sets, n_group_sets * sizeof(uint64_t), hipMemcpyHostToDevice));
@@ -640,7 +650,7 @@ int nhdfit_set_dictionary(nhdfit_ctx* c, uint32_t max_cores_per_numa, uint32_t m
 int nhdfit_reserve_nodes(nhdfit_ctx* c, uint32_t capacity, uint64_t global_base) {
     if (!c) return NHDFIT_E_INVAL;
     HIPCHK(c, hipSetDevice(c->dev));
-    { int rc_ = sync_all(c); if (rc_) return rc_; }
+    TRY(sync_all(c));
     if (capacity > c->capacity) {
         c->n = 0;                                   // growing drops the contents: the caller re-uploads
         c->n_wide = 0; c->wide_index.clear();
@@ -663,7 +673,7 @@ int nhdfit_set_node_count(nhdfit_ctx* c, uint32_t n) {
     if (n > c->capacity) return fail(c, NHDFIT_E_INVAL, "node count %u exceeds reserved capacity %u", n, c->capacity);
     if (n != c->n) {
         HIPCHK(c, hipSetDevice(c->dev));
-        { int rc_ = sync_all(c); if (rc_) return rc_; }     // mapping phases of steps in flight still read the old count
+        TRY(sync_all(c));     // mapping phases of steps in flight still read the old count
         c->rec_all = true;                                  // the padding records of the last chunk move
         c->n_items = 0;
         c->n = n;
@@ -686,7 +696,7 @@ int nhdfit_upload_nodes(nhdfit_ctx* c, uint32_t first, uint32_t count, const nhd
     if (!p0 || !p1 || !p2 || !p3 || !p4 || !det) return fail(c, NHDFIT_E_INVAL, "NULL plane");
     if ((uint64_t)first + count > c->capacity) return fail(c, NHDFIT_E_INVAL, "upload [%u,%u) exceeds capacity %u", first, first + count, c->capacity);
     HIPCHK(c, hipSetDevice(c->dev));
-    { int rc_ = sync_all(c); if (rc_) return rc_; }     // a step in flight must not see a half-written record
+    TRY(sync_all(c));     // a step in flight must not see a half-written record
     if (first + count > c->n) { c->rec_all = true; c->n_items = 0; }   // the node count changes: the last chunk's padding moves
     else if (c->rec_lo == c->rec_hi) { c->rec_lo = first; c->rec_hi = first + count; }
     else { c->rec_lo = std::min(c->rec_lo, first); c->rec_hi = std::max(c->rec_hi, first + count); }
@@ -797,8 +807,8 @@ namespace {
 int stage_requests(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, bool defer_small_copies, bool defer_request_copy, size_t tail_bytes = 0);
 int finish_deferred_copies(nhdfit_ctx* c) {
     const uint32_t tiles = (c->P + kTile - 1) / kTile;
-    if (c->reqs_deferred) HIPCHK(c, hipMemcpyAsync(c->reqs.p, c->pin_reqs.p, (size_t)c->P * sizeof(nhdfit_req), hipMemcpyHostToDevice, c->stream));
-    if (c->wcls_deferred) HIPCHK(c, hipMemcpyAsync(c->tile_wcls.p, c->pin_wcls.p, tiles, hipMemcpyHostToDevice, c->stream));
+    if (c->reqs_deferred) HIPCHK(c, hipMemcpyAsync(c->reqs.p, c->pin_reqs.p, (size_t)c->P * sizeof(nhdfit_req), hipMemcpyHostToDevice, c->streams.use(0)));
+    if (c->wcls_deferred) HIPCHK(c, hipMemcpyAsync(c->tile_wcls.p, c->pin_wcls.p, tiles, hipMemcpyHostToDevice, c->streams.use(0)));
     c->reqs_deferred = c->wcls_deferred = false;
     return NHDFIT_OK;
 }
@@ -821,14 +831,15 @@ int stage_requests(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, bool defer
         fprintf(stderr, "[nhdfit]   stage P=%u %s %.1f us\n", P, what, std::chrono::duration<double, std::micro>(t1 - t_prev).count());
         t_prev = t1;
     };
-    // (a single-launch find that saw its word left the streams idle, and nothing has been asked of the runtime since: asking the first
-    // stream would only make it reap that launch now - ~12 us of every batch call)
-    const bool idle = c->known_idle && c->ev_pending == 0;
+    // (no stream holds a mark - a single-launch find of a batch that saw its word left them so, and nothing was enqueued since: asking
+    // the first stream would only make the runtime reap that launch now - ~12 us of every batch call)
+    const bool idle = c->streams.all_clean() && c->ev_pending == 0;
     HIPCHK(c, hipSetDevice(c->dev));
     if (!idle) {
-        { int rc_ = sync_all(c); if (rc_) return rc_; }
-        { int rc_ = drain_events(c); if (rc_) return rc_; }
-    }
+        TRY(sync_all(c));
+        TRY(drain_events(c));
+    } else
+        TRY(check_skipped_waits(c, "stage_requests"));
     lap("streams idle, events read");
     for (Pipe& p : c->pipe) p.n_dig = p.n_fit = p.n_shaped = p.n_chosen = p.n_finished = 0;
     c->n_enq = 0;
@@ -850,7 +861,7 @@ int stage_requests(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, bool defer
     for (Pipe& p : c->pipe)
         if (tiles > p.dig_count.cap) {                 // (the digest role leaves its arrival counters at zero: cleared when the buffer is new)
             HIPCHK(c, p.dig_count.reserve(std::max<size_t>(tiles, 256)));
-            HIPCHK(c, hipMemsetAsync(p.dig_count.p, 0, p.dig_count.cap * sizeof(uint32_t), c->stream));
+            HIPCHK(c, hipMemsetAsync(p.dig_count.p, 0, p.dig_count.cap * sizeof(uint32_t), c->streams.use(0)));
         }
     for (Pipe& p : c->pipe)
         for (int b = 0; b < kBufs; ++b) {
@@ -885,18 +896,18 @@ int stage_requests(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, bool defer
     // ONE copy: the batch in four pieces, each piece's transfer beside the next piece's gather, was measured and is slower - every copy
     // command costs the copy engine ~10 us before its first byte moves (config 4: 0.166 -> 0.193 ms per call, profiles/r05)
     c->reqs_deferred = defer_request_copy;
-    if (!defer_request_copy) HIPCHK(c, hipMemcpyAsync(c->reqs.p, sorted, (size_t)P * sizeof *reqs, hipMemcpyHostToDevice, c->stream));
+    if (!defer_request_copy) HIPCHK(c, hipMemcpyAsync(c->reqs.p, sorted, (size_t)P * sizeof *reqs, hipMemcpyHostToDevice, c->streams.use(0)));
     HIPCHK(c, c->tile_wcls.reserve(tiles));
     HIPCHK(c, c->pin_wcls.reserve(tiles));
     memcpy(c->pin_wcls.p, c->h_tile_wcls.data(), tiles);
     c->wcls_deferred = defer_small_copies;
-    if (!defer_small_copies) HIPCHK(c, hipMemcpyAsync(c->tile_wcls.p, c->pin_wcls.p, tiles, hipMemcpyHostToDevice, c->stream));
+    if (!defer_small_copies) HIPCHK(c, hipMemcpyAsync(c->tile_wcls.p, c->pin_wcls.p, tiles, hipMemcpyHostToDevice, c->streams.use(0)));
     c->P = P;
     c->hp_rows = (uint32_t)hp_max + 2;
     c->n_items = 0;                                 // the fit role's work items are rebuilt at the next step
     c->use_cand = false;
     lap("copies enqueued");
-    { int rc_ = refresh_layouts(c); if (rc_) return rc_; }
+    TRY(refresh_layouts(c));
     lap("layouts");
     // a node's C row depends on the pair table's dimension: a batch that changes it has the chunks' records dealt to the lanes again
     // (ensure_records, in front of the batch's first step) - a full tile and more only: smaller batches are latency, not throughput
@@ -929,7 +940,7 @@ int order_chunks(nhdfit_ctx* c, uint32_t first_chunk, uint32_t n_chunks, bool ev
     for (int w = 0; w < kWClasses; ++w) { o.rec[w] = c->rec[w].p; o.bt[w] = c->rec_bt[w].p; }
     o.first_chunk = first_chunk; o.n_chunks = n_chunks;
     o.pair_D[0] = c->order_D[0] == ~0u ? 0u : c->order_D[0]; o.pair_D[1] = c->order_D[1] == ~0u ? 0u : c->order_D[1];
-    LAUNCH(c, k_xorder, dim3((n_chunks * (uint32_t)kWClasses + 3) / 4), dim3(256), 0, c->stream, o);
+    hipLaunchKernelGGL(k_xorder, dim3((n_chunks * (uint32_t)kWClasses + 3) / 4), dim3(256), 0, c->streams.use(0), o);
     HIPCHK(c, hipGetLastError());
     return NHDFIT_OK;
 }
@@ -949,23 +960,23 @@ int ensure_records(nhdfit_ctx* c) {
         if (!c->n || c->rec_all || !c->rec[0].p || !c->rec[1].p) return NHDFIT_OK;
         CrowArgs k;
         k.rec[0] = c->rec[0].p; k.rec[1] = c->rec[1].p; k.npad = (c->n + 63) & ~63u; k.D[0] = c->crow_D[0]; k.D[1] = c->crow_D[1];
-        LAUNCH(c, k_xcrow, dim3((k.npad + 255) / 256), dim3(256), 0, c->stream, k);
+        hipLaunchKernelGGL(k_xcrow, dim3((k.npad + 255) / 256), dim3(256), 0, c->streams.use(0), k);
         HIPCHK(c, hipGetLastError());
         return NHDFIT_OK;
     };
     if (!c->rec_all && c->rec_lo == c->rec_hi) {
         if (c->n && (crow || (c->ord_all && deal))) {           // the records stand, a staged batch changed the pair table's dimension
-            { int rc_ = sync_all(c); if (rc_) return rc_; }     // (steps in flight read the records)
+            TRY(sync_all(c));     // (steps in flight read the records)
             c->staged_gen++;
-            if (crow) { int rc_ = rewrite_crows(); if (rc_) return rc_; }
-            if (c->ord_all && deal) { int rc_ = order_chunks(c, 0, all_chunks, true); if (rc_) return rc_; }
+            if (crow) TRY(rewrite_crows());
+            if (c->ord_all && deal) TRY(order_chunks(c, 0, all_chunks, true));
         }
         c->ord_all = false;
         return NHDFIT_OK;
     }
     c->staged_gen++;                                            // (its kernels run on pipe 0's stream)
     if (!c->n) { c->rec_all = false; c->rec_lo = c->rec_hi = 0; c->ord_all = false; return NHDFIT_OK; }
-    if (crow) { { int rc_ = sync_all(c); if (rc_) return rc_; } { int rc_ = rewrite_crows(); if (rc_) return rc_; } }
+    if (crow) { TRY(sync_all(c)); TRY(rewrite_crows()); }
     const uint32_t npad = (c->n + 63) & ~63u;
     uint32_t dealt_first = 0, dealt_count = 0;
     for (int pass = 0; pass < 2; ++pass) {
@@ -987,15 +998,15 @@ int ensure_records(nhdfit_ctx* c) {
         r.crow_D[0] = c->crow_D[0]; r.crow_D[1] = c->crow_D[1];
         const dim3 grid((count + 255) / 256), block(256);
         if (pass == 0) {
-            LAUNCH(c, k_xkeys, grid, block, 0, c->stream, r);
-            LAUNCH(c, k_xassign, dim3(1), dim3(1024), 0, c->stream, r.x);
+            hipLaunchKernelGGL(k_xkeys, grid, block, 0, c->streams.use(0), r);
+            hipLaunchKernelGGL(k_xassign, dim3(1), dim3(1024), 0, c->streams.use(0), r.x);
         }
-        LAUNCH(c, k_xrecords, grid, block, 0, c->stream, r);
+        hipLaunchKernelGGL(k_xrecords, grid, block, 0, c->streams.use(0), r);
         HIPCHK(c, hipGetLastError());
         if (pass == 1) break;
         uint32_t nx[2] = {0, 0};
-        HIPCHK(c, hipMemcpyAsync(nx, c->xnx.p, sizeof nx, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, wait_stream(c->stream));
+        HIPCHK(c, hipMemcpyAsync(nx, c->xnx.p, sizeof nx, hipMemcpyDeviceToHost, c->streams.use(0)));
+        HIPCHK(c, c->streams.wait(0));
         if (nx[1] || nx[0] > kXSlots / 2) return fail(c, NHDFIT_E_LIMIT, "more than %u distinct (free GPUs, NIC signature) node classes", kXSlots / 2);
         if (nx[0] != c->nx)                                     // new classes: a table image digested ahead of its fit has no X rows for
             for (Pipe& p : c->pipe)                             // them - it is digested again (nhdfit_enqueue_step looks here first)
@@ -1016,18 +1027,17 @@ int ensure_records(nhdfit_ctx* c) {
         }
         if (nx[0] <= c->x_cap) break;
         // more classes than provisioned rows: every hot-section offset moves -> staged tables and all records are redone
-        { int rc_ = sync_all(c); if (rc_) return rc_; }
+        TRY(sync_all(c));
         c->x_cap = x_capacity(nx[0]);
         c->rec_all = true;
         for (Pipe& p : c->pipe) p.n_dig = std::min(p.n_dig, p.n_fit);   // every staged table image is redone
-        int rc = refresh_layouts(c);
-        if (rc) return rc;
+        TRY(refresh_layouts(c));
     }
     if (deal) {
         // a few rewritten chunks (the scheduler's loop: one commit, then the next find) stay in node order until the next full deal -
         // a launch of its own in front of a 60 us call costs more than their bank conflicts
         const bool every = c->ord_all || c->rec_all;
-        if (every || dealt_count >= 16) { int rc_ = order_chunks(c, every ? 0 : dealt_first, every ? all_chunks : dealt_count, every); if (rc_) return rc_; }
+        if (every || dealt_count >= 16) TRY(order_chunks(c, every ? 0 : dealt_first, every ? all_chunks : dealt_count, every));
     }
     c->ord_all = false;
     c->rec_all = false;
@@ -1106,7 +1116,7 @@ int build_items(nhdfit_ctx* c, uint32_t nw, bool batch_find = false) {
         for (uint32_t t = 0; t < tiles; ++t) per_tile[t] = 0;
         for (const FitItem& it : items) per_tile[it.tile]++;
     } else
-        HIPCHK(c, hipMemcpyAsync(c->items.p, c->pin_items.p, items.size() * sizeof(FitItem), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->items.p, c->pin_items.p, items.size() * sizeof(FitItem), hipMemcpyHostToDevice, c->streams.use(0)));
     c->n_items = (uint32_t)items.size();
     c->staged_gen++;
     return NHDFIT_OK;
@@ -1166,18 +1176,17 @@ void fill_fit_args(nhdfit_ctx* c, Pipe& p, int bf, double now, FitArgs& f, bool 
 // One launch of the step kernel with every role that has work (see k_step).  `with_fit`: the fit role for step
 // n_fit plus the digest of step n_fit + 1; `flushing`: nothing new will follow, drain the mapping phases.
 int launch_step(nhdfit_ctx* c, Pipe& p, bool with_fit, bool with_digest, double now, bool flushing) {
-    c->side_streams_used = true;
     const uint32_t P = c->P, tiles = (P + kTile - 1) / kTile;
     const uint32_t chunks = (c->n + 63) / 64;
     const bool big = c->geom_big;
     const uint32_t block = big ? 512 : 256, nw = block / 64;
     const bool small_map = c->want_map && c->n_big_pods < P;
-    if (with_fit || with_digest) { int rc_ = ensure_records(c); if (rc_) return rc_; }
-    if (with_fit && !c->n_items) { int rc_ = build_items(c, nw); if (rc_) return rc_; }
+    if (with_fit || with_digest) TRY(ensure_records(c));
+    if (with_fit && !c->n_items) TRY(build_items(c, nw));
     if (&p != &c->pipe[0] && p.seen_gen != c->staged_gen) {
         // what pipe 0's stream staged since this pipe last looked (requests, work items, node records) is in front of this launch
-        HIPCHK(c, hipEventRecord(p.ev_staged, c->pipe[0].stream));
-        HIPCHK(c, hipStreamWaitEvent(p.stream, p.ev_staged, 0));
+        HIPCHK(c, hipEventRecord(p.ev_staged, c->streams.use(0)));
+        HIPCHK(c, hipStreamWaitEvent(c->streams.use(p.k), p.ev_staged, 0));
         p.seen_gen = c->staged_gen;
     }
 
@@ -1207,7 +1216,7 @@ int launch_step(nhdfit_ctx* c, Pipe& p, bool with_fit, bool with_digest, double 
         const uint64_t ready = c->comm && !flushing && p.n_fit ? p.n_fit - 1 : p.n_fit;
         if (p.n_shaped < ready) {
             const int b = (int)(p.n_shaped % kBufs);
-            if (c->comm) HIPCHK(c, hipStreamWaitEvent(p.stream, p.ev_red[b], 0));
+            if (c->comm) HIPCHK(c, hipStreamWaitEvent(c->streams.use(p.k), p.ev_red[b], 0));
             HIPCHK(c, p.shape_keys[b].reserve((size_t)tiles * kTile));
             HIPCHK(c, p.shape_res[b].reserve((size_t)tiles * kTile));
             HIPCHK(c, p.shape_slot[b].reserve(P));
@@ -1252,8 +1261,8 @@ int launch_step(nhdfit_ctx* c, Pipe& p, bool with_fit, bool with_digest, double 
         HIPCHK(c, c->role_clock.reserve(32));
         unsigned long long init[32] = {0};
         for (int k = 0; k < 5; ++k) { init[2 * k] = ~0ull; init[2 * k + 1] = 0; }
-        HIPCHK(c, hipMemcpyAsync(c->role_clock.p, init, sizeof init, hipMemcpyHostToDevice, p.stream));
-        HIPCHK(c, wait_stream(p.stream));
+        HIPCHK(c, hipMemcpyAsync(c->role_clock.p, init, sizeof init, hipMemcpyHostToDevice, c->streams.use(p.k)));
+        HIPCHK(c, c->streams.wait(p.k));
         a.role_clock = c->role_clock.p;
         a.fit.clk = c->role_clock.p + 16;                  // per-block phases of the fit role (FitArgs::clk)
     }
@@ -1261,29 +1270,29 @@ int launch_step(nhdfit_ctx* c, Pipe& p, bool with_fit, bool with_digest, double 
     if (timed && c->ev_pending == kEventRing) { int rc = drain_events(c); if (rc) return rc; }
     static const bool enq_prof = tune_env("NHDFIT_ENQ_PROF") != nullptr;
     const auto t_ev0 = enq_prof ? std::chrono::steady_clock::now() : std::chrono::steady_clock::time_point();
-    if (timed) HIPCHK(c, hipEventRecord(c->ev[c->ev_pending][0], p.stream));
+    if (timed) HIPCHK(c, hipEventRecord(c->ev[c->ev_pending][0], c->streams.use(p.k)));
     const auto t_l0 = enq_prof ? std::chrono::steady_clock::now() : std::chrono::steady_clock::time_point();
     if (enq_prof) c->enq_events_us += std::chrono::duration<double, std::micro>(t_l0 - t_ev0).count();
     if (c->x_spill) {               // more node classes than LDS rows: the variant whose fit role reads the rest from global memory
-        if (big) LAUNCH(c, (k_step<512, true>), dim3(grid), dim3(512), lds, p.stream, a);
-        else     LAUNCH(c, (k_step<256, true>), dim3(grid), dim3(256), lds, p.stream, a);
+        if (big) hipLaunchKernelGGL((k_step<512, true>), dim3(grid), dim3(512), lds, c->streams.use(p.k), a);
+        else     hipLaunchKernelGGL((k_step<256, true>), dim3(grid), dim3(256), lds, c->streams.use(p.k), a);
     } else
 #ifdef NHDFIT_TUNING         // (role_kernels / split are switched by the tuning build's environment only: never set in libnhdfit.so)
     if (c->role_kernels) {
         const uint32_t nb[5] = {a.nb_choose, a.nb_shapes, a.nb_finish, a.nb_digest, nb_fit};
-        if (nb[0]) LAUNCH(c, (k_role<512, 0>), dim3(nb[0]), dim3(512), 0, p.stream, a);
-        if (nb[1]) LAUNCH(c, (k_role<512, 1>), dim3(nb[1]), dim3(512), map_lds_bytes<512>(), p.stream, a);
-        if (nb[2]) LAUNCH(c, (k_role<512, 2>), dim3(nb[2]), dim3(512), map_lds_bytes<512>(), p.stream, a);
-        if (nb[3]) LAUNCH(c, (k_role<512, 3>), dim3(nb[3]), dim3(512), kDigestLds, p.stream, a);
-        if (nb[4]) LAUNCH(c, (k_role<512, 4>), dim3(nb[4]), dim3(512), lds, p.stream, a);
+        if (nb[0]) hipLaunchKernelGGL((k_role<512, 0>), dim3(nb[0]), dim3(512), 0, c->streams.use(p.k), a);
+        if (nb[1]) hipLaunchKernelGGL((k_role<512, 1>), dim3(nb[1]), dim3(512), map_lds_bytes<512>(), c->streams.use(p.k), a);
+        if (nb[2]) hipLaunchKernelGGL((k_role<512, 2>), dim3(nb[2]), dim3(512), map_lds_bytes<512>(), c->streams.use(p.k), a);
+        if (nb[3]) hipLaunchKernelGGL((k_role<512, 3>), dim3(nb[3]), dim3(512), kDigestLds, c->streams.use(p.k), a);
+        if (nb[4]) hipLaunchKernelGGL((k_role<512, 4>), dim3(nb[4]), dim3(512), lds, c->streams.use(p.k), a);
     } else
     if (grid == nb_fit && c->split) {
-        if (big) LAUNCH(c, (k_fit_only<512>), dim3(grid), dim3(512), lds, p.stream, a.fit);
-        else     LAUNCH(c, (k_fit_only<256>), dim3(grid), dim3(256), lds, p.stream, a.fit);
+        if (big) hipLaunchKernelGGL((k_fit_only<512>), dim3(grid), dim3(512), lds, c->streams.use(p.k), a.fit);
+        else     hipLaunchKernelGGL((k_fit_only<256>), dim3(grid), dim3(256), lds, c->streams.use(p.k), a.fit);
     } else
 #endif
-    if (big) LAUNCH(c, (k_step<512>), dim3(grid), dim3(512), lds, p.stream, a);
-    else     LAUNCH(c, (k_step<256>), dim3(grid), dim3(256), lds, p.stream, a);
+    if (big) hipLaunchKernelGGL((k_step<512>), dim3(grid), dim3(512), lds, c->streams.use(p.k), a);
+    else     hipLaunchKernelGGL((k_step<256>), dim3(grid), dim3(256), lds, c->streams.use(p.k), a);
     HIPCHK(c, hipGetLastError());
     if (enq_prof) c->enq_launch_us += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_l0).count();
     if (with_fit && c->n_wide) {
@@ -1296,18 +1305,18 @@ int launch_step(nhdfit_ctx* c, Pipe& p, bool with_fit, bool with_digest, double 
         wa.nm = c->want_bitmap ? reinterpret_cast<unsigned long long*>(p.nm.p) : nullptr; wa.chunks = chunks;
         wa.score = p.score[bf].p; wa.global_base = c->global_base; wa.share = c->sharing ? c->wide_share.p : nullptr;
         const uint64_t pairs = (uint64_t)c->n_wide * P;
-        LAUNCH(c, k_wide_eval, dim3((uint32_t)((pairs + 255) / 256)), dim3(256), 0, p.stream, wa);
+        hipLaunchKernelGGL(k_wide_eval, dim3((uint32_t)((pairs + 255) / 256)), dim3(256), 0, c->streams.use(p.k), wa);
         HIPCHK(c, hipGetLastError());
     }
     if (timed) {
         const auto t_e1 = enq_prof ? std::chrono::steady_clock::now() : std::chrono::steady_clock::time_point();
-        HIPCHK(c, hipEventRecord(c->ev[c->ev_pending][1], p.stream));
+        HIPCHK(c, hipEventRecord(c->ev[c->ev_pending][1], c->streams.use(p.k)));
         c->ev_kind[c->ev_pending++] = with_fit ? 0 : 1;
         if (enq_prof) c->enq_events_us += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_e1).count();
     }
     if (a.role_clock) {
         unsigned long long t[32];
-        HIPCHK(c, wait_stream(p.stream));
+        HIPCHK(c, c->streams.wait(p.k));
         HIPCHK(c, hipMemcpy(t, c->role_clock.p, sizeof t, hipMemcpyDeviceToHost));
         if (t[24]) {
             const double nb = (double)t[24];
@@ -1325,20 +1334,19 @@ int launch_step(nhdfit_ctx* c, Pipe& p, bool with_fit, bool with_digest, double 
     p.n_finished += did_finish; p.n_chosen += did_choose; p.n_shaped += did_shapes;
     if (with_digest) p.n_dig++;
     if (with_fit) {
-        hipStream_t after = p.stream;           // where the scores of this step become final
-        if (c->comm) {      // one communicator -> its collectives stay on one stream (s_red), in step order
-            HIPCHK(c, hipEventRecord(p.ev_fit[bf], p.stream));
-            HIPCHK(c, hipStreamWaitEvent(c->s_red, p.ev_fit[bf], 0));
-            ncclResult_t r = (c->known_idle = false, g_rccl).AllReduce(p.score[bf].p, p.score[bf].p, P, ncclUint64, ncclMax, c->comm, c->s_red);
-            if (r != ncclSuccess) return fail(c, NHDFIT_E_RCCL, "ncclAllReduce: %s", g_rccl.GetErrorString(r));
-            after = c->s_red;
+        int after = p.k;                        // the stream on which the scores of this step become final
+        if (c->comm) {      // one communicator -> its collectives stay on one stream (the reduce stream), in step order
+            HIPCHK(c, hipEventRecord(p.ev_fit[bf], c->streams.use(p.k)));
+            HIPCHK(c, hipStreamWaitEvent(c->streams.use(kRed), p.ev_fit[bf], 0));
+            TRY(rccl(c, kRed, "ncclAllReduce", &Rccl::AllReduce, p.score[bf].p, p.score[bf].p, P, ncclUint64, ncclMax, c->comm));
+            after = kRed;
         }
         if (c->want_map && c->n_big_pods) {      // pods with 4 proc groups: generic set model (scratch-heavy, kept out of k_step)
             const dim3 mg((P + kMapWaves - 1) / kMapWaves), mb(64 * kMapWaves);
-            LAUNCH(c, k_map<true>, mg, mb, 0, after, map_args(bf));
+            hipLaunchKernelGGL(k_map<true>, mg, mb, 0, c->streams.use(after), map_args(bf));
             HIPCHK(c, hipGetLastError());
         }
-        if (c->comm) HIPCHK(c, hipEventRecord(p.ev_red[bf], c->s_red));
+        if (c->comm) HIPCHK(c, hipEventRecord(p.ev_red[bf], c->streams.use(kRed)));
         p.n_fit++;
         // no mapping roles for this step (output switched off, or only 4-group pods): nothing to catch up on later
         if (!small_map) p.n_shaped = p.n_chosen = p.n_finished = p.n_fit;
@@ -1358,9 +1366,9 @@ int launch_step(nhdfit_ctx* c, Pipe& p, bool with_fit, bool with_digest, double 
 int convert_rows(nhdfit_ctx* c, Pipe& p) {
     const uint32_t chunks = (c->n + 63) / 64, tiles = (c->P + kTile - 1) / kTile;
     HIPCHK(c, c->bitmap.reserve((size_t)chunks * c->P));
-    LAUNCH(c, k_rows, dim3((tiles * chunks + 3) / 4), dim3(256), 0, p.stream, p.nm.p, c->bitmap.p, chunks, c->P);
+    hipLaunchKernelGGL(k_rows, dim3((tiles * chunks + 3) / 4), dim3(256), 0, c->streams.use(p.k), p.nm.p, c->bitmap.p, chunks, c->P);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, wait_stream(p.stream));
+    HIPCHK(c, c->streams.wait(p.k));
     return NHDFIT_OK;
 }
 
@@ -1369,7 +1377,7 @@ int convert_rows_t(nhdfit_ctx* c, Pipe& p) {
     const uint32_t chunks = (c->n + 63) / 64, tiles = (c->P + kTile - 1) / kTile;
     const uint32_t groups = (chunks + kRowsTChunks - 1) / kRowsTChunks;
     HIPCHK(c, c->rows_t.reserve((size_t)chunks * c->P));
-    LAUNCH(c, k_rows_t, dim3((tiles * groups + 3) / 4), dim3(256), 0, p.stream, p.nm.p, c->rows_t.p, chunks, c->P);
+    hipLaunchKernelGGL(k_rows_t, dim3((tiles * groups + 3) / 4), dim3(256), 0, c->streams.use(p.k), p.nm.p, c->rows_t.p, chunks, c->P);
     HIPCHK(c, hipGetLastError());
     return NHDFIT_OK;
 }
@@ -1381,8 +1389,7 @@ int flush_pipeline(nhdfit_ctx* c) {
     for (Pipe& p : c->pipe) {
         if (role_drain || c->role_kernels || c->split) {
             while (p.n_finished < p.n_fit) {
-                int rc = launch_step(c, p, false, false, 0.0, true);
-                if (rc) return rc;
+                TRY(launch_step(c, p, false, false, 0.0, true));
             }
             continue;
         }
@@ -1394,23 +1401,22 @@ int flush_pipeline(nhdfit_ctx* c) {
             a.h = make_shape_args(c, p, 0);
             while (a.nsteps < (uint32_t)kDrainSteps && p.n_finished + a.nsteps < p.n_fit) {
                 const int b = (int)((p.n_finished + a.nsteps) % kBufs);
-                if (c->comm) HIPCHK(c, hipStreamWaitEvent(p.stream, p.ev_red[b], 0));      // the step's scores are final behind its all-reduce
+                if (c->comm) HIPCHK(c, hipStreamWaitEvent(c->streams.use(p.k), p.ev_red[b], 0));      // the step's scores are final behind its all-reduce
                 a.m[a.nsteps++] = make_map_args(c, p, b);
             }
-            c->side_streams_used = true;
             const bool drain_prof = tune_env("NHDFIT_DRAIN_PROF") != nullptr;      // tuning aid: where a drain launch's time goes
             if (drain_prof) {
                 HIPCHK(c, c->role_clock.reserve(16));
                 unsigned long long init[16] = {0};
                 init[7] = ~0ull;
-                HIPCHK(c, hipMemcpyAsync(c->role_clock.p, init, sizeof init, hipMemcpyHostToDevice, p.stream));
+                HIPCHK(c, hipMemcpyAsync(c->role_clock.p, init, sizeof init, hipMemcpyHostToDevice, c->streams.use(p.k)));
                 a.clk = c->role_clock.p;
             }
-            LAUNCH(c, k_map_tiles, dim3(a.nsteps * tiles), dim3(256), map_tile_lds_bytes<256>(), p.stream, a);
+            hipLaunchKernelGGL(k_map_tiles, dim3(a.nsteps * tiles), dim3(256), map_tile_lds_bytes<256>(), c->streams.use(p.k), a);
             HIPCHK(c, hipGetLastError());
             if (drain_prof) {
                 unsigned long long t[16];
-                HIPCHK(c, wait_stream(p.stream));
+                HIPCHK(c, c->streams.wait(p.k));
                 HIPCHK(c, hipMemcpy(t, c->role_clock.p, sizeof t, hipMemcpyDeviceToHost));
                 fprintf(stderr, "[nhdfit] drain of %u step(s) x %u tiles: staged +%.2f, NIC bits / masks / key +%.2f, shapes de-duplicated +%.2f, state machine +%.2f, "
                                 "generic shapes +%.2f, finish +%.2f us after a block's start (latest block each); first block start to last block end %.2f us\n",
@@ -1466,14 +1472,12 @@ static int enqueue_step(nhdfit_ctx* c, double now) {
     c->last_pipe = which;
     // the mirror may have changed since the last step (uploads, commits, deltas between two steps of one staged batch): node
     // records first - new node classes put the digests that ran ahead back (ensure_records), and they are redone below
-    { int rc_ = ensure_records(c); if (rc_) return rc_; }
+    TRY(ensure_records(c));
     if (p.n_dig <= p.n_fit) {                        // this pipe's first step after staging (or after such a change): its digest has not run yet
-        int rc = launch_step(c, p, false, true, now, false);
-        if (rc) return rc;
+        TRY(launch_step(c, p, false, true, now, false));
     }
     if (c->split) {                                  // profiling aid: side roles and fit role as two launches
-        int rc = launch_step(c, p, false, true, now, false);
-        if (rc) return rc;
+        TRY(launch_step(c, p, false, true, now, false));
         return launch_step(c, p, true, false, now, false);
     }
     return launch_step(c, p, true, true, now, false);
@@ -1491,42 +1495,40 @@ int nhdfit_fetch(nhdfit_ctx* c, uint64_t* score_out, uint64_t* bitmap_out, nhdfi
     if (!c) return NHDFIT_E_INVAL;
     Pipe& p = c->pipe[c->last_pipe];
     if (!c->P || !p.n_fit) return fail(c, NHDFIT_E_STATE, "nothing staged / no step enqueued");
-    c->side_streams_used = true;                                // (the copies below ride the last step's pipe)
     HIPCHK(c, hipSetDevice(c->dev));
     if (map_out && !c->want_map) return fail(c, NHDFIT_E_STATE, "mapping output is disabled");
     const uint32_t P = c->P;
     const int b = (int)((p.n_fit - 1) % kBufs);               // results of the most recent step
     // the launches that finish the mappings still in flight, the copies behind them on the same stream, ONE wait
-    { int rc_ = flush_pipeline(c); if (rc_) return rc_; }
-    if (c->comm) HIPCHK(c, wait_stream(c->s_red));
+    TRY(flush_pipeline(c));
+    if (c->comm) HIPCHK(c, c->streams.wait(kRed));
     if (map_out && c->n_wide) {
         // winners that are wide nodes: their mappings from the general set model, over what the mapping roles left for them
         constexpr uint32_t kWideMapThreads = 512;
         HIPCHK(c, c->wide_scratch.reserve((size_t)kWideMapThreads * kWideScratchWords));
         HIPCHK(c, c->wide_flags.reserve(4));
-        HIPCHK(c, hipMemsetAsync(c->wide_flags.p, 0, 4 * sizeof(uint32_t), p.stream));
+        HIPCHK(c, hipMemsetAsync(c->wide_flags.p, 0, 4 * sizeof(uint32_t), c->streams.use(p.k)));
         WideMapArgs wm;
         memset(&wm, 0, sizeof wm);
         wm.wide = c->wide.p; wm.n_wide = c->n_wide; wm.reqs = c->reqs.p; wm.P = P; wm.caps = c->caps.p;
         wm.score = p.score[b].p; wm.global_base = c->global_base; wm.n = c->n; wm.out = p.maps[b].p;
         wm.scratch = c->wide_scratch.p; wm.flags = c->wide_flags.p; wm.share = c->sharing ? c->wide_share.p : nullptr;
-        LAUNCH(c, k_wide_map, dim3(kWideMapThreads), dim3(64), 0, p.stream, wm);
+        hipLaunchKernelGGL(k_wide_map, dim3(kWideMapThreads), dim3(64), 0, c->streams.use(p.k), wm);
         HIPCHK(c, hipGetLastError());
         uint32_t fl[4] = {0, 0, 0, 0};
-        HIPCHK(c, hipMemcpyAsync(fl, c->wide_flags.p, sizeof fl, hipMemcpyDeviceToHost, p.stream));
-        HIPCHK(c, wait_stream(p.stream));
+        HIPCHK(c, hipMemcpyAsync(fl, c->wide_flags.p, sizeof fl, hipMemcpyDeviceToHost, c->streams.use(p.k)));
+        HIPCHK(c, c->streams.wait(p.k));
         if (fl[0]) return fail(c, NHDFIT_E_LIMIT, "the set model of a wide node's mapping outgrew its table");
     }
     if (score_out) {
         HIPCHK(c, c->pin_score.reserve(P));
-        HIPCHK(c, hipMemcpyAsync(c->pin_score.p, p.score[b].p, (size_t)P * 8, hipMemcpyDeviceToHost, p.stream));
+        HIPCHK(c, hipMemcpyAsync(c->pin_score.p, p.score[b].p, (size_t)P * 8, hipMemcpyDeviceToHost, c->streams.use(p.k)));
     }
     if (map_out) {
         HIPCHK(c, c->pin_maps.reserve(P));
-        HIPCHK(c, hipMemcpyAsync(c->pin_maps.p, p.maps[b].p, (size_t)P * sizeof(nhdfit_mapping), hipMemcpyDeviceToHost, p.stream));
+        HIPCHK(c, hipMemcpyAsync(c->pin_maps.p, p.maps[b].p, (size_t)P * sizeof(nhdfit_mapping), hipMemcpyDeviceToHost, c->streams.use(p.k)));
     }
-    int rc = nhdfit_sync(c);
-    if (rc) return rc;
+    TRY(nhdfit_sync(c));
     if (score_out)
         for (uint32_t i = 0; i < P; ++i) score_out[c->perm[i]] = c->pin_score.p[i];
     if (map_out)
@@ -1534,7 +1536,7 @@ int nhdfit_fetch(nhdfit_ctx* c, uint64_t* score_out, uint64_t* bitmap_out, nhdfi
     if (bitmap_out) {
         if (!c->want_bitmap) return fail(c, NHDFIT_E_STATE, "bitmap output is disabled");
         const size_t chunks = (c->n + 63) / 64;
-        { int rc_ = convert_rows(c, p); if (rc_) return rc_; }
+        TRY(convert_rows(c, p));
         std::vector<uint64_t> tmp(chunks * P);
         HIPCHK(c, hipMemcpy(tmp.data(), c->bitmap.p, chunks * P * 8, hipMemcpyDeviceToHost));
         for (size_t ch = 0; ch < chunks; ++ch)
@@ -1564,8 +1566,8 @@ int find_small(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, double now, co
     if (hp_max > kMaxHpRows - 2) return 1;
     HIPCHK(c, hipSetDevice(c->dev));
     if (c->P) {                                                 // a staged batch: its steps may be in flight on either pipe
-        { int rc_ = sync_all(c); if (rc_) return rc_; }
-        { int rc_ = drain_events(c); if (rc_) return rc_; }
+        TRY(sync_all(c));
+        TRY(drain_events(c));
     }
     Pipe& p = c->pipe[0];
     for (Pipe& q : c->pipe) q.n_dig = q.n_fit = q.n_shaped = q.n_chosen = q.n_finished = 0;
@@ -1587,7 +1589,7 @@ int find_small(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, double now, co
         // (consecutive pods of one node group come with the same mask: it is uploaded when it changes)
         c->cand_shadow.clear();
         e = c->cand.reserve(chunks);
-        if (e == hipSuccess) e = hipMemcpyAsync(c->cand.p, cand, (size_t)chunks * 8, hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(c->cand.p, cand, (size_t)chunks * 8, hipMemcpyHostToDevice, c->streams.use(0));
         if (e == hipSuccess) c->cand_shadow.assign(cand, cand + chunks);
     }
     if (e != hipSuccess) { c->P = 0; return fail(c, NHDFIT_E_HIP, "small find: %s", hipGetErrorString(e)); }
@@ -1646,30 +1648,21 @@ int find_small(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, double now, co
     }
     const auto t_launch = std::chrono::steady_clock::now();
     c->P = 0;                                                   // nothing is staged for nhdfit_enqueue_step / nhdfit_fetch
-    if (lone) LAUNCH(c, (k_find1<256>), dim3(a1.nb), dim3(256), kLoneLds + map_tile_lds_bytes<256>(), c->stream, a1);
-    else LAUNCH(c, (k_find<256>), dim3(a.s.nb_digest + a.s.nb_fit), dim3(256), lds, c->stream, a);
+    if (lone) hipLaunchKernelGGL((k_find1<256>), dim3(a1.nb), dim3(256), kLoneLds + map_tile_lds_bytes<256>(), c->streams.use(0), a1);
+    else hipLaunchKernelGGL((k_find<256>), dim3(a.s.nb_digest + a.s.nb_fit), dim3(256), lds, c->streams.use(0), a);
     HIPCHK(c, hipGetLastError());
     uint32_t seen = 0;
-    for (uint32_t spins = 1;; ++spins) {
-        seen = __atomic_load_n(&h->flag, __ATOMIC_ACQUIRE);
-        if (seen == seq || seen == kFindAborted) break;
-        if ((spins & 255u) == 0 && std::chrono::steady_clock::now() - t_launch > std::chrono::microseconds(500)) {
-            HIPCHK(c, wait_stream(c->stream));         // a long launch (or host memory the device does not write through): wait for its end
-            seen = __atomic_load_n(&h->flag, __ATOMIC_ACQUIRE);
-            break;
-        }
-        __builtin_ia32_pause();
-    }
+    TRY(poll_word(c, &h->flag, seq, kFindAborted, t_launch, 500, 0, seen));
     if (seen != seq) {                                          // the launch gave up on a wait: counters back to zero, staged path
-        HIPCHK(c, wait_stream(c->stream));
-        HIPCHK(c, hipMemsetAsync(c->find_sync.p, 0, 8 * sizeof(uint32_t), c->stream));
+        HIPCHK(c, c->streams.wait(0));
+        HIPCHK(c, hipMemsetAsync(c->find_sync.p, 0, 8 * sizeof(uint32_t), c->streams.use(0)));
         h->flag = 0;
         return 1;
     }
     if (clocks) {
         const double us_seen = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_launch).count();
         unsigned long long t[10];
-        HIPCHK(c, wait_stream(c->stream));
+        HIPCHK(c, c->streams.wait(0));
         HIPCHK(c, hipMemcpy(t, c->role_clock.p, sizeof t, hipMemcpyDeviceToHost));
         unsigned long long first = ~0ull;
         for (int k = 0; k < 5; ++k) first = t[2 * k] < first ? t[2 * k] : first;
@@ -1692,11 +1685,10 @@ int find_small(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, double now, co
         staged_order(reqs, P, c->perm);
         uint64_t* send = c->pin_score.p + kTile;
         for (uint32_t k = 0; k < P; ++k) send[k] = h->score[c->perm[k]];
-        HIPCHK(c, hipMemcpyAsync(c->find_red.p, send, (size_t)P * 8, hipMemcpyHostToDevice, c->s_red));
-        ncclResult_t r = (c->known_idle = false, g_rccl).AllReduce(c->find_red.p, c->find_red.p, P, ncclUint64, ncclMax, c->comm, c->s_red);
-        if (r != ncclSuccess) return fail(c, NHDFIT_E_RCCL, "ncclAllReduce: %s", g_rccl.GetErrorString(r));
-        HIPCHK(c, hipMemcpyAsync(c->pin_score.p, c->find_red.p, (size_t)P * 8, hipMemcpyDeviceToHost, c->s_red));
-        HIPCHK(c, wait_stream(c->s_red));
+        HIPCHK(c, hipMemcpyAsync(c->find_red.p, send, (size_t)P * 8, hipMemcpyHostToDevice, c->streams.use(kRed)));
+        TRY(rccl(c, kRed, "ncclAllReduce", &Rccl::AllReduce, c->find_red.p, c->find_red.p, P, ncclUint64, ncclMax, c->comm));
+        HIPCHK(c, hipMemcpyAsync(c->pin_score.p, c->find_red.p, (size_t)P * 8, hipMemcpyDeviceToHost, c->streams.use(kRed)));
+        HIPCHK(c, c->streams.wait(kRed));
         for (uint32_t k = 0; k < P; ++k) {
             const uint32_t i = c->perm[k];
             if (c->pin_score.p[k] != h->score[i]) memset(&h->maps[i], 0, sizeof(nhdfit_mapping));
@@ -1763,7 +1755,7 @@ int find_batch(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, double now, co
     if (sync_words > c->findn_sync_words) {
         const uint32_t words = std::max(sync_words, 2u + 2u * 256u);
         HIPCHK(c, c->findn_sync.reserve(words));
-        HIPCHK(c, hipMemsetAsync(c->findn_sync.p, 0, (size_t)words * sizeof(uint32_t), c->stream));
+        HIPCHK(c, hipMemsetAsync(c->findn_sync.p, 0, (size_t)words * sizeof(uint32_t), c->streams.use(0)));
         c->findn_sync_words = words;
     }
     uint32_t seq = ++c->find_seq;
@@ -1788,7 +1780,7 @@ int find_batch(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, double now, co
     const size_t items_bytes = (size_t)c->n_items * sizeof(FitItem), counts_bytes = (size_t)tiles * sizeof(uint32_t);
     if (host_reqs || items_bytes + counts_bytes + tiles > tail_cap) {
         // everything where the staging left it: the launch reads the page-locked block (few tiles: a few dozen reads over the link)
-        if (!host_reqs) { HIPCHK(c, hipMemcpyAsync(c->reqs.p, c->pin_reqs.p, (size_t)P * sizeof(nhdfit_req), hipMemcpyHostToDevice, c->stream)); c->reqs_deferred = false; }
+        if (!host_reqs) { HIPCHK(c, hipMemcpyAsync(c->reqs.p, c->pin_reqs.p, (size_t)P * sizeof(nhdfit_req), hipMemcpyHostToDevice, c->streams.use(0))); c->reqs_deferred = false; }
         else { a.s.digest.reqs = c->pin_reqs.p; a.s.finish_m.reqs = c->pin_reqs.p; }
         a.s.fit.items = reinterpret_cast<const FitItem*>(c->pin_items.p);
         a.tile_items = reinterpret_cast<const uint32_t*>(c->pin_items.p + items_bytes);
@@ -1798,7 +1790,7 @@ int find_batch(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, double now, co
         const uint8_t* tail_d = reinterpret_cast<const uint8_t*>(c->reqs.p + P);
         memcpy(tail_h, c->pin_items.p, items_bytes + counts_bytes);
         memcpy(tail_h + items_bytes + counts_bytes, c->pin_wcls.p, tiles);
-        HIPCHK(c, hipMemcpyAsync(c->reqs.p, c->pin_reqs.p, (size_t)P * sizeof(nhdfit_req) + items_bytes + counts_bytes + tiles, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->reqs.p, c->pin_reqs.p, (size_t)P * sizeof(nhdfit_req) + items_bytes + counts_bytes + tiles, hipMemcpyHostToDevice, c->streams.use(0)));
         c->reqs_deferred = false;
         a.s.fit.items = reinterpret_cast<const FitItem*>(tail_d);
         a.tile_items = reinterpret_cast<const uint32_t*>(tail_d + items_bytes);
@@ -1809,23 +1801,14 @@ int find_batch(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, double now, co
     lds = std::max(lds, std::max(kDigestLds, map_tile_lds_bytes<256>()));
     lap("records, items, arguments");
     const auto t_launch = std::chrono::steady_clock::now();
-    LAUNCH(c, (k_findn<256>), dim3(a.nb_lead + a.s.nb_fit), dim3(256), lds, c->stream, a);
+    hipLaunchKernelGGL((k_findn<256>), dim3(a.nb_lead + a.s.nb_fit), dim3(256), lds, c->streams.use(0), a);
     HIPCHK(c, hipGetLastError());
     lap("launch call");
     uint32_t seen = 0;
-    for (uint32_t spins = 1;; ++spins) {
-        seen = __atomic_load_n(h_flag, __ATOMIC_ACQUIRE);
-        if (seen == seq || seen == kFindAborted) break;
-        if ((spins & 255u) == 0 && std::chrono::steady_clock::now() - t_launch > std::chrono::microseconds(2000)) {
-            HIPCHK(c, wait_stream(c->stream));                  // a long launch (or host memory the device does not write through): wait for its end
-            seen = __atomic_load_n(h_flag, __ATOMIC_ACQUIRE);
-            break;
-        }
-        __builtin_ia32_pause();
-    }
+    TRY(poll_word(c, h_flag, seq, kFindAborted, t_launch, 2000, 0, seen));
     if (seen != seq) {                                          // the launch gave up on a wait: counters back to zero, staged path
-        HIPCHK(c, wait_stream(c->stream));
-        HIPCHK(c, hipMemsetAsync(c->findn_sync.p, 0, (size_t)c->findn_sync_words * sizeof(uint32_t), c->stream));
+        HIPCHK(c, c->streams.wait(0));
+        HIPCHK(c, hipMemsetAsync(c->findn_sync.p, 0, (size_t)c->findn_sync_words * sizeof(uint32_t), c->streams.use(0)));
         *h_flag = 0;
         c->n_items = 0;                                         // (the step's own work items: 512-thread blocks)
         return to_steps();
@@ -1839,7 +1822,7 @@ int find_batch(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, double now, co
     c->stats.nodes = c->n; c->stats.nsig = c->nsig; c->stats.ncls = c->ncls; c->stats.lds_bytes = c->lds_bytes;
     c->stats.batch_finds++;
     c->P = 0; c->n_items = 0;                                   // nothing stays staged for nhdfit_enqueue_step / nhdfit_fetch
-    c->known_idle = true;                                       // (the word came behind everything this call put on the stream)
+    c->streams.pipe0_drained_by_its_last_word();                // (the word came behind everything this call put on the stream)
     (void)chunks;
     return NHDFIT_OK;
 }
@@ -1901,7 +1884,7 @@ int nhdfit_wide_download(nhdfit_ctx* c, nhdfit_wide_node* out, uint32_t cap, uin
     if (!c->n_wide || !out) return NHDFIT_OK;
     if (cap < c->n_wide) return fail(c, NHDFIT_E_INVAL, "%u wide records, room for %u", c->n_wide, cap);
     HIPCHK(c, hipSetDevice(c->dev));
-    HIPCHK(c, wait_stream(c->stream));
+    HIPCHK(c, c->streams.wait(0));
     HIPCHK(c, hipMemcpy(out, c->wide.p, (size_t)c->n_wide * sizeof *out, hipMemcpyDeviceToHost));
     return NHDFIT_OK;
 }
@@ -1922,7 +1905,7 @@ int nhdfit_wide_upload(nhdfit_ctx* c, uint32_t first, uint32_t count, const nhdf
     }
     if (!n_wide && !c->n_wide) return NHDFIT_OK;
     HIPCHK(c, hipSetDevice(c->dev));
-    { int rc_ = sync_all(c); if (rc_) return rc_; }
+    TRY(sync_all(c));
     std::vector<nhdfit_wide_node> cur(c->n_wide), next;
     if (c->n_wide) HIPCHK(c, hipMemcpy(cur.data(), c->wide.p, cur.size() * sizeof cur[0], hipMemcpyDeviceToHost));   // (commits may have changed them)
     size_t k = 0;
@@ -1944,7 +1927,7 @@ int nhdfit_wide_upload(nhdfit_ctx* c, uint32_t first, uint32_t count, const nhdf
 int nhdfit_wide_share_upload(nhdfit_ctx* c, const nhdfit_wide_share* share, uint32_t n_wide) {
     if (!c) return NHDFIT_E_INVAL;
     HIPCHK(c, hipSetDevice(c->dev));
-    { int rc_ = sync_all(c); if (rc_) return rc_; }
+    TRY(sync_all(c));
     if (!share) { c->sharing = false; return NHDFIT_OK; }
     if (n_wide != c->n_wide) return fail(c, NHDFIT_E_INVAL, "%u speed_used records for %u wide records", n_wide, c->n_wide);
     if (c->n_wide != c->n) return fail(c, NHDFIT_E_STATE, "ENABLE_SHARING: every node of the mirror must be a wide record (%u of %u are)", c->n_wide, c->n);
@@ -1960,7 +1943,7 @@ int nhdfit_wide_share_download(nhdfit_ctx* c, nhdfit_wide_share* out, uint32_t c
     if (!c->sharing || !c->n_wide) return NHDFIT_OK;
     if (!out || cap < c->n_wide) return fail(c, NHDFIT_E_INVAL, "room for %u speed_used records, the mirror holds %u", cap, c->n_wide);
     HIPCHK(c, hipSetDevice(c->dev));
-    { int rc_ = sync_all(c); if (rc_) return rc_; }
+    TRY(sync_all(c));
     HIPCHK(c, hipMemcpy(out, c->wide_share.p, (size_t)c->n_wide * sizeof *out, hipMemcpyDeviceToHost));
     return NHDFIT_OK;
 }
@@ -1981,16 +1964,16 @@ int nhdfit_wide_commit(nhdfit_ctx* c, uint32_t node, const nhdfit_req* req, cons
             return fail(c, NHDFIT_E_INVAL, "mapping: group %u uses NIC ordinal %d", g, (int)map->nic_idx[g]);
     }
     HIPCHK(c, hipSetDevice(c->dev));
-    { int rc_ = sync_all(c); if (rc_) return rc_; }             // steps in flight read the wide records
+    TRY(sync_all(c));             // steps in flight read the wide records
     HIPCHK(c, c->wide_place.reserve(1));
     WideCommitArgs wa;
     memset(&wa, 0, sizeof wa);
     wa.wide = c->wide.p; wa.slot = (uint32_t)slot; wa.req = *req; wa.map = *map; wa.busy_time = busy_time; wa.out = c->wide_place.p;
     wa.share = c->sharing ? c->wide_share.p : nullptr;
-    LAUNCH(c, k_wide_commit, dim3(1), dim3(64), 0, c->stream, wa);
+    hipLaunchKernelGGL(k_wide_commit, dim3(1), dim3(64), 0, c->streams.use(0), wa);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(place_out, c->wide_place.p, sizeof *place_out, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, wait_stream(c->stream));
+    HIPCHK(c, hipMemcpyAsync(place_out, c->wide_place.p, sizeof *place_out, hipMemcpyDeviceToHost, c->streams.use(0)));
+    HIPCHK(c, c->streams.wait(0));
     return NHDFIT_OK;
 }
 
@@ -2001,18 +1984,18 @@ int nhdfit_big_find(nhdfit_ctx* c, const nhdfit_big_req* reqs, uint32_t P, doubl
     if (P > 65535u) return fail(c, NHDFIT_E_LIMIT, "%u big requests in one call (<= 65535)", P);
     if (c->n && !c->ncls) return fail(c, NHDFIT_E_STATE, "set the dictionary first (nhdfit_set_dictionary: the NIC capacity classes)");
     HIPCHK(c, hipSetDevice(c->dev));
-    { int rc_ = sync_all(c); if (rc_) return rc_; }             // (a rare call: no need to run beside steps in flight)
+    TRY(sync_all(c));             // (a rare call: no need to run beside steps in flight)
     const size_t chunks = (c->n + 63) / 64;
     HIPCHK(c, c->big_reqs.reserve(P));
     HIPCHK(c, c->big_score.reserve(P));
     HIPCHK(c, c->big_maps.reserve(P));
     HIPCHK(c, c->big_flags.reserve(4));
-    HIPCHK(c, hipMemcpyAsync(c->big_reqs.p, reqs, (size_t)P * sizeof *reqs, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->big_score.p, 0, (size_t)P * 8, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->big_flags.p, 0, 4 * sizeof(uint32_t), c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->big_reqs.p, reqs, (size_t)P * sizeof *reqs, hipMemcpyHostToDevice, c->streams.use(0)));
+    HIPCHK(c, hipMemsetAsync(c->big_score.p, 0, (size_t)P * 8, c->streams.use(0)));
+    HIPCHK(c, hipMemsetAsync(c->big_flags.p, 0, 4 * sizeof(uint32_t), c->streams.use(0)));
     if (cand && chunks) {
         HIPCHK(c, c->big_cand.reserve(chunks));
-        HIPCHK(c, hipMemcpyAsync(c->big_cand.p, cand, chunks * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->big_cand.p, cand, chunks * sizeof(uint64_t), hipMemcpyHostToDevice, c->streams.use(0)));
     }
     const uint32_t units = c->n + c->n_wide;
     if (units) {
@@ -2022,14 +2005,13 @@ int nhdfit_big_find(nhdfit_ctx* c, const nhdfit_big_req* reqs, uint32_t P, doubl
         ea.wide = c->wide.p; ea.n_wide = c->n_wide; ea.reqs = c->big_reqs.p; ea.P = P; ea.caps = c->caps.p; ea.busy_from = busy_threshold(now);
         ea.share = c->sharing ? c->wide_share.p : nullptr;
         ea.cand = cand && chunks ? c->big_cand.p : nullptr; ea.score = c->big_score.p; ea.global_base = c->global_base; ea.flags = c->big_flags.p;
-        LAUNCH(c, k_big_eval, dim3((units + 63) / 64, P), dim3(64), 0, c->stream, ea);
+        hipLaunchKernelGGL(k_big_eval, dim3((units + 63) / 64, P), dim3(64), 0, c->streams.use(0), ea);
         HIPCHK(c, hipGetLastError());
     }
     if (c->comm) {      // sharded: one all-reduce(max) of the P packed scores picks the cluster's winners; the owner maps (k_big_map skips the rest)
-        HIPCHK(c, wait_stream(c->stream));
-        ncclResult_t r = (c->known_idle = false, g_rccl).AllReduce(c->big_score.p, c->big_score.p, P, ncclUint64, ncclMax, c->comm, c->s_red);
-        if (r != ncclSuccess) return fail(c, NHDFIT_E_RCCL, "ncclAllReduce: %s", g_rccl.GetErrorString(r));
-        HIPCHK(c, wait_stream(c->s_red));
+        HIPCHK(c, c->streams.wait(0));
+        TRY(rccl(c, kRed, "ncclAllReduce", &Rccl::AllReduce, c->big_score.p, c->big_score.p, P, ncclUint64, ncclMax, c->comm));
+        HIPCHK(c, c->streams.wait(kRed));
     }
     if (map_out && c->n) {
         // set tables of one mapping: sized for the call's largest group count on the mirror's widest node (2 sockets, 8 groups:
@@ -2049,16 +2031,16 @@ int nhdfit_big_find(nhdfit_ctx* c, const nhdfit_big_req* reqs, uint32_t P, doubl
         ma.stride = stride; ma.slots_g = (int32_t)wide_table_slots(wide_ipow(umax, gmax)); ma.slots_c = (int32_t)wide_table_slots(wide_ipow(umax, gmax + 1)); ma.workers = workers;
         ma.lds_tables = lds_tables ? 1u : 0u;
         if (lds_tables) HIPCHK(c, hipFuncSetAttribute((const void*)k_big_map, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-        LAUNCH(c, k_big_map, dim3(workers), dim3(64), lds_tables ? stride * sizeof(int32_t) : 0, c->stream, ma);
+        hipLaunchKernelGGL(k_big_map, dim3(workers), dim3(64), lds_tables ? stride * sizeof(int32_t) : 0, c->streams.use(0), ma);
         HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(map_out, c->big_maps.p, (size_t)P * sizeof *map_out, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(map_out, c->big_maps.p, (size_t)P * sizeof *map_out, hipMemcpyDeviceToHost, c->streams.use(0)));
     } else if (map_out) {
         memset(map_out, 0, (size_t)P * sizeof *map_out);
     }
     uint32_t fl[4] = {0, 0, 0, 0};
-    HIPCHK(c, hipMemcpyAsync(score_out, c->big_score.p, (size_t)P * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(fl, c->big_flags.p, sizeof fl, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, wait_stream(c->stream));
+    HIPCHK(c, hipMemcpyAsync(score_out, c->big_score.p, (size_t)P * 8, hipMemcpyDeviceToHost, c->streams.use(0)));
+    HIPCHK(c, hipMemcpyAsync(fl, c->big_flags.p, sizeof fl, hipMemcpyDeviceToHost, c->streams.use(0)));
+    HIPCHK(c, c->streams.wait(0));
     c->stats.big_nic_steps_max = std::max(c->stats.big_nic_steps_max, fl[2]);
     if (fl[1]) return fail(c, NHDFIT_E_LIMIT, "a big request's NIC stage ran out of search budget on some node (%u steps per pod and node)", (unsigned)NHDFIT_BIG_NIC_BUDGET);
     if (fl[0]) return fail(c, NHDFIT_E_LIMIT, "the set model of a big request's mapping outgrew its table");
@@ -2082,7 +2064,7 @@ int nhdfit_big_commit(nhdfit_ctx* c, uint32_t node, const nhdfit_big_req* req, c
             return fail(c, NHDFIT_E_INVAL, "mapping: group %u uses NIC ordinal %d", g, (int)map->nic_idx[g]);
     }
     HIPCHK(c, hipSetDevice(c->dev));
-    { int rc_ = sync_all(c); if (rc_) return rc_; }             // the commit writes the mirror: steps in flight on either pipe read it
+    TRY(sync_all(c));             // the commit writes the mirror: steps in flight on either pipe read it
     HIPCHK(c, c->big_place.reserve(1));
     BigCommitArgs ba;
     memset(&ba, 0, sizeof ba);
@@ -2090,10 +2072,10 @@ int nhdfit_big_commit(nhdfit_ctx* c, uint32_t node, const nhdfit_big_req* req, c
     ba.wide = c->wide.p; ba.slot = slot; ba.node = node; ba.req = *req; ba.map = *map; ba.busy_time = busy_time; ba.sigs = sig_table(c);
     ba.share = c->sharing ? c->wide_share.p : nullptr;
     ba.out = c->big_place.p;
-    LAUNCH(c, k_big_commit, dim3(1), dim3(64), 0, c->stream, ba);
+    hipLaunchKernelGGL(k_big_commit, dim3(1), dim3(64), 0, c->streams.use(0), ba);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(place_out, c->big_place.p, sizeof *place_out, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, wait_stream(c->stream));
+    HIPCHK(c, hipMemcpyAsync(place_out, c->big_place.p, sizeof *place_out, hipMemcpyDeviceToHost, c->streams.use(0)));
+    HIPCHK(c, c->streams.wait(0));
     if (slot < 0) {                                             // the node's records (X class, free-core counts) follow its planes
         if (c->rec_lo == c->rec_hi) { c->rec_lo = node; c->rec_hi = node + 1; }
         else { c->rec_lo = std::min(c->rec_lo, node); c->rec_hi = std::max(c->rec_hi, node + 1); }
@@ -2178,7 +2160,7 @@ int schedule_batch_general(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, do
             if (r2 && !rc) rc = r2;
         }
         if (!wide_before.empty()) {
-            HIPCHK(c, wait_stream(c->stream));
+            HIPCHK(c, c->streams.wait(0));
             HIPCHK(c, hipMemcpy(c->wide.p, wide_before.data(), wide_before.size() * sizeof wide_before[0], hipMemcpyHostToDevice));
             if (!share_before.empty()) HIPCHK(c, hipMemcpy(c->wide_share.p, share_before.data(), share_before.size() * sizeof share_before[0], hipMemcpyHostToDevice));
         }
@@ -2203,13 +2185,12 @@ int nhdfit_schedule_batch(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, dou
         explicit CommOff(nhdfit_ctx* c_) : c(c_), saved(c_->comm) { c->comm = nullptr; }
         ~CommOff() { c->comm = saved; }
     };
-    if (c->comm) { int rc_ = sync_all(c); if (rc_) return rc_; }   // (steps of a staged batch still carry their all-reduce)
+    if (c->comm) TRY(sync_all(c));   // (steps of a staged batch still carry their all-reduce)
     CommOff comm_off(c);
     if (!std::isfinite(now)) return fail(c, NHDFIT_E_INVAL, "now must be finite (a placed node is busy at `now`)");
     HIPCHK(c, hipSetDevice(c->dev));
     c->wide_places_last.clear();
     if (c->n_wide) return schedule_batch_general(c, reqs, P, now, cand, apply, node_out, map_out, place_out, status_out, n_done);
-    hipStream_t sm = c->stream;
     Pipe& p = c->pipe[0];                                       // (the one step a freshly staged batch enqueues runs on pipe 0)
     const uint32_t chunks = (c->n + 63) / 64;
     const uint32_t tiles = (P + kTile - 1) / kTile;
@@ -2261,10 +2242,10 @@ int nhdfit_schedule_batch(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, dou
                 if (pass == 0) c->tn_n = at;
             }
         }
-        HIPCHK(c, hipMemcpyAsync(c->order.p, order_h, 2 * (size_t)P * sizeof(uint32_t), hipMemcpyHostToDevice, sm));
-        LAUNCH(c, k_nogpu, dim3(chunks), dim3(64), 0, sm, c->p2.p, c->n, c->nogpu.p);
+        HIPCHK(c, hipMemcpyAsync(c->order.p, order_h, 2 * (size_t)P * sizeof(uint32_t), hipMemcpyHostToDevice, c->streams.use(0)));
+        hipLaunchKernelGGL(k_nogpu, dim3(chunks), dim3(64), 0, c->streams.use(0), c->p2.p, c->n, c->nogpu.p);
         const int b0 = (int)((p.n_fit - 1) % kBufs);
-        LAUNCH(c, k_tile_masks, dim3(tiles), dim3(64), 0, sm, p.hdr[b0].p, tiles, c->tile_masks.p);
+        hipLaunchKernelGGL(k_tile_masks, dim3(tiles), dim3(64), 0, c->streams.use(0), p.hdr[b0].p, tiles, c->tile_masks.p);
         HIPCHK(c, hipGetLastError());
     }
     // pod-major verdict rows of the snapshot + empty taken / first-touch state (again before a fallback pass)
@@ -2272,15 +2253,14 @@ int nhdfit_schedule_batch(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, dou
     // decision engine's words)
     uint32_t queue_len = 0;
     auto reset_scan_state = [&](bool engine) -> int {
-        int rc_ = convert_rows_t(c, p);
-        if (rc_) return rc_;
+        TRY(convert_rows_t(c, p));
         SeqResetArgs ra;
         memset(&ra, 0, sizeof ra);
         ra.taken = c->taken.p; ra.chunks = chunks ? chunks : 1; ra.touched = c->touched.p; ra.n = c->n;
         ra.counters = c->seq_counters.p; ra.flags = c->seq_flags.p;
         if (engine) { ra.ctrl = c->seq_ctrl.p; ra.mat = c->seq_mat.p; ra.queue = c->seq_queue.p; ra.queue_len = queue_len; }
         const uint32_t most = std::max(std::max(ra.chunks, ra.n), ra.queue_len);
-        LAUNCH(c, k_seq_reset, dim3(std::min<uint32_t>((most + 255) / 256, 1024u)), dim3(256), 0, sm, ra);
+        hipLaunchKernelGGL(k_seq_reset, dim3(std::min<uint32_t>((most + 255) / 256, 1024u)), dim3(256), 0, c->streams.use(0), ra);
         HIPCHK(c, hipGetLastError());
         return NHDFIT_OK;
     };
@@ -2309,12 +2289,12 @@ int nhdfit_schedule_batch(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, dou
         HIPCHK(c, hipFuncSetAttribute(seq_pods == 16 ? (const void*)k_seq<16> : (const void*)k_seq<8>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
         const bool seq_prof = tune_env("NHDFIT_SEQ_PROF") != nullptr;
         if (seq_prof) { HIPCHK(c, c->role_clock.reserve(16)); g.prof = c->role_clock.p; }
-        if (seq_pods == 16) LAUNCH(c, k_seq<16>, dim3(1), dim3(1024), seq_lds, sm, g);
-        else LAUNCH(c, k_seq<8>, dim3(1), dim3(512), seq_lds, sm, g);
+        if (seq_pods == 16) hipLaunchKernelGGL(k_seq<16>, dim3(1), dim3(1024), seq_lds, c->streams.use(0), g);
+        else hipLaunchKernelGGL(k_seq<8>, dim3(1), dim3(512), seq_lds, c->streams.use(0), g);
         HIPCHK(c, hipGetLastError());
         if (seq_prof) {
             unsigned long long t[16];
-            HIPCHK(c, wait_stream(sm));
+            HIPCHK(c, c->streams.wait(0));
             HIPCHK(c, hipMemcpy(t, c->role_clock.p, sizeof t, hipMemcpyDeviceToHost));
             const double per = 0.01 / (double)(t[3] ? t[3] : 1);
             fprintf(stderr, "[nhdfit] k_seq wave 0 per round: node load %.1f, NIC bits %.1f, mapping %.1f, commit %.1f, write-back %.1f us\n",
@@ -2325,13 +2305,13 @@ int nhdfit_schedule_batch(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, dou
                     t[11] * per, t[12] * per, t[13] * per, t[14] * per, (double)t[15] / (double)(t[3] ? t[3] : 1));
         }
         uint32_t counters[4] = {0, 0, 0, 0};
-        HIPCHK(c, hipMemcpyAsync(counters, c->seq_counters.p, sizeof counters, hipMemcpyDeviceToHost, sm));
-        HIPCHK(c, wait_stream(sm));
+        HIPCHK(c, hipMemcpyAsync(counters, c->seq_counters.p, sizeof counters, hipMemcpyDeviceToHost, c->streams.use(0)));
+        HIPCHK(c, c->streams.wait(0));
         done = counters[1];
         return NHDFIT_OK;
     };
     auto undo_all = [&]() -> int {                              // every node this batch touched goes back to its first-touch copy
-        LAUNCH(c, k_undo, dim3(P), dim3(64), 0, sm, sa);
+        hipLaunchKernelGGL(k_undo, dim3(P), dim3(64), 0, c->streams.use(0), sa);
         HIPCHK(c, hipGetLastError());
         return NHDFIT_OK;
     };
@@ -2372,7 +2352,7 @@ int nhdfit_schedule_batch(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, dou
         // The decision engine (seq2_kernel.h): one block decides, the rest of the grid commits.
         const uint32_t* list_dev = c->order.p + P;              // [the pods without GPUs | every other pod] (uploaded behind the order)
         const uint32_t n_n = c->tn_n, n_g = P - c->tn_n;
-        LAUNCH(c, k_decide_prep, dim3((P + 255) / 256), dim3(256), 0, sm, list_dev, P, c->order.p, p.score[b].p, c->global_base, c->seq_ent.p);
+        hipLaunchKernelGGL(k_decide_prep, dim3((P + 255) / 256), dim3(256), 0, c->streams.use(0), list_dev, P, c->order.p, p.score[b].p, c->global_base, c->seq_ent.p);
         HIPCHK(c, hipGetLastError());
         DecideArgs qa;
         memset(&qa, 0, sizeof qa);
@@ -2390,12 +2370,12 @@ int nhdfit_schedule_batch(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, dou
         if (c->use_choose_tab && dyn + lds_slice(kChooseEntries) <= room112) { qa.lds_choose = 1; dyn += lds_slice(kChooseEntries); }
         HIPCHK(c, hipFuncSetAttribute(any_g4 ? (const void*)k_decide<true> : (const void*)k_decide<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
         static const uint32_t workers = tune_env("NHDFIT_SEQ_WORKERS") ? (uint32_t)atoi(tune_env("NHDFIT_SEQ_WORKERS")) : (uint32_t)kWorkerBlocks;   // tuning aid
-        if (any_g4) LAUNCH(c, k_decide<true>, dim3(1 + (workers ? workers : 1u)), dim3(64 * kDecideWaves), dyn, sm, qa);
-        else LAUNCH(c, k_decide<false>, dim3(1 + (workers ? workers : 1u)), dim3(64 * kDecideWaves), dyn, sm, qa);
+        if (any_g4) hipLaunchKernelGGL(k_decide<true>, dim3(1 + (workers ? workers : 1u)), dim3(64 * kDecideWaves), dyn, c->streams.use(0), qa);
+        else hipLaunchKernelGGL(k_decide<false>, dim3(1 + (workers ? workers : 1u)), dim3(64 * kDecideWaves), dyn, c->streams.use(0), qa);
         HIPCHK(c, hipGetLastError());
         uint32_t flags[4] = {0, 0, 0, 0};
-        HIPCHK(c, hipMemcpyAsync(flags, c->seq_flags.p, sizeof flags, hipMemcpyDeviceToHost, sm));
-        HIPCHK(c, wait_stream(sm));
+        HIPCHK(c, hipMemcpyAsync(flags, c->seq_flags.p, sizeof flags, hipMemcpyDeviceToHost, c->streams.use(0)));
+        HIPCHK(c, c->streams.wait(0));
         if (tune_env("NHDFIT_SEQ_PROF")) {
             uint32_t ctl[32];
             HIPCHK(c, hipMemcpy(ctl, c->seq_ctrl.p, sizeof ctl, hipMemcpyDeviceToHost));
@@ -2424,8 +2404,8 @@ int nhdfit_schedule_batch(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, dou
     }
     if (!apply) { if ((rc = undo_all())) return rc; }
     c->seq_host.resize(P);
-    HIPCHK(c, hipMemcpyAsync(c->seq_host.data(), c->seq_out.p, P * sizeof(SeqResult), hipMemcpyDeviceToHost, sm));
-    if (place_out) HIPCHK(c, hipMemcpyAsync(place_out, c->seq_place.p, (size_t)P * sizeof(nhdfit_placement), hipMemcpyDeviceToHost, sm));
+    HIPCHK(c, hipMemcpyAsync(c->seq_host.data(), c->seq_out.p, P * sizeof(SeqResult), hipMemcpyDeviceToHost, c->streams.use(0)));
+    if (place_out) HIPCHK(c, hipMemcpyAsync(place_out, c->seq_place.p, (size_t)P * sizeof(nhdfit_placement), hipMemcpyDeviceToHost, c->streams.use(0)));
     rc = nhdfit_sync(c);
     if (rc) return rc;
     *n_done = decided;
@@ -2452,8 +2432,7 @@ int nhdfit_find_sequential(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, do
                            int64_t* node_out, nhdfit_mapping* map_out, int32_t* status_out) {
     // the mirror is left as it was (k_undo): a NIC state without a signature cannot be patched in, the batch fails
     uint32_t done = 0;
-    int rc = nhdfit_schedule_batch(c, reqs, P, now, cand, 0, node_out, map_out, nullptr, status_out, &done);
-    if (rc) return rc;
+    TRY(nhdfit_schedule_batch(c, reqs, P, now, cand, 0, node_out, map_out, nullptr, status_out, &done));
     if (done < P) return fail(c, NHDFIT_E_STATE, "pod %u left its node in a NIC state the dictionary has no signature for: "
                               "use nhdfit_schedule_batch (apply) and intern it", done - 1);
     return NHDFIT_OK;
@@ -2478,9 +2457,10 @@ int nhdfit_commit(nhdfit_ctx* c, uint32_t node, const nhdfit_req* req, const nhd
     // the commit writes the planes: steps in flight on EITHER pipe (their fit roles, digests running ahead, pending mapping
     // phases) read them - wait for both, as every other writer of the mirror does (nhdfit_upload_nodes)
     // ... unless nothing can be in flight anywhere but on this very stream: no batch is staged (the single-launch finds leave none) and
-    // the other pipes' streams and the reduce stream have carried nothing since they were last waited for - then stream order is all
-    // the commit needs (the scheduler's pod-at-a-time loop: asking the stream whether the find's launch has retired cost ~10 us per pod)
-    if (c->P || c->side_streams_used) { int rc_ = sync_all(c); if (rc_) return rc_; }
+    // the ledger holds no mark for another pipe's stream or for the reduce stream - then stream order is all the commit needs (the
+    // scheduler's pod-at-a-time loop: asking the stream whether the find's launch has retired cost ~10 us per pod)
+    if (c->P || !c->streams.sides_clean()) TRY(sync_all(c));
+    else TRY(check_skipped_waits(c, "nhdfit_commit"));
     if (!c->commit_host) return fail(c, NHDFIT_E_STATE, "no host block for the commit's result");
     CommitArgs ca;
     memset(&ca, 0, sizeof ca);
@@ -2489,18 +2469,13 @@ int nhdfit_commit(nhdfit_ctx* c, uint32_t node, const nhdfit_req* req, const nhd
     const uint32_t seq = ++c->commit_seq ? c->commit_seq : ++c->commit_seq;                 // (never 0: the block's resting value)
     ca.host = c->commit_host; ca.seq = seq; ca.ncls = c->ncls;
     const auto t_launch = std::chrono::steady_clock::now();
-    LAUNCH(c, k_commit, dim3(1), dim3(64), 0, c->stream, ca);       // (both pipes are idle: sync_all above)
+    hipLaunchKernelGGL(k_commit, dim3(1), dim3(64), 0, c->streams.use(0), ca);       // (behind whatever pipe 0 still holds; nothing else is in flight)
     HIPCHK(c, hipGetLastError());
     // the placement arrives in the fine-grained host block behind the sequence number: poll it (a launch that takes longer than
     // half a millisecond - it cannot, short of a fault - is waited for on its stream)
-    for (uint32_t spins = 1; __atomic_load_n(&c->commit_host->flag, __ATOMIC_ACQUIRE) != seq; ++spins) {
-        if ((spins & 255u) == 0 && std::chrono::steady_clock::now() - t_launch > std::chrono::microseconds(500)) {
-            HIPCHK(c, wait_stream(c->stream));
-            if (__atomic_load_n(&c->commit_host->flag, __ATOMIC_ACQUIRE) != seq) return fail(c, NHDFIT_E_HIP, "the commit kernel ended without publishing its placement");
-            break;
-        }
-        __builtin_ia32_pause();
-    }
+    uint32_t seen = 0;
+    TRY(poll_word(c, &c->commit_host->flag, seq, seq, t_launch, 500, 0, seen));
+    if (seen != seq) return fail(c, NHDFIT_E_HIP, "the commit kernel ended without publishing its placement");
     *place_out = c->commit_host->place;
     if (c->rec_lo == c->rec_hi) { c->rec_lo = node; c->rec_hi = node + 1; }
     else { c->rec_lo = std::min(c->rec_lo, node); c->rec_hi = std::max(c->rec_hi, node + 1); }
@@ -2514,7 +2489,7 @@ int nhdfit_upload_origin(nhdfit_ctx* c, uint32_t first, uint32_t count, const nh
     if ((uint64_t)first + count > c->capacity) return fail(c, NHDFIT_E_INVAL, "upload [%u,%u) exceeds capacity %u", first, first + count, c->capacity);
     if (first > c->origin_hi) return fail(c, NHDFIT_E_INVAL, "origin records [%u,%u) are missing", c->origin_hi, first);
     HIPCHK(c, hipSetDevice(c->dev));
-    HIPCHK(c, wait_stream(c->stream));                  // a delta kernel in flight may still write its records
+    HIPCHK(c, c->streams.wait(0));                  // a delta kernel in flight may still write its records
     HIPCHK(c, hipMemcpy(c->origin.p + first, origin, count * sizeof *origin, hipMemcpyHostToDevice));
     c->origin_hi = std::max(c->origin_hi, first + count);
     return NHDFIT_OK;
@@ -2547,20 +2522,20 @@ int nhdfit_apply_deltas(nhdfit_ctx* c, const nhdfit_delta* deltas, uint32_t n, u
     const uint32_t n_runs = (uint32_t)run.size();
     run.push_back(n);
     HIPCHK(c, hipSetDevice(c->dev));
-    { int rc_ = sync_all(c); if (rc_) return rc_; }             // steps in flight on either pipe (fit, digest, the mapping phases flushed here) read
+    TRY(sync_all(c));             // steps in flight on either pipe (fit, digest, the mapping phases flushed here) read
                                                                 // the nodes as they were matched: the deltas wait for both pipes
     HIPCHK(c, c->deltas.reserve(n)); HIPCHK(c, c->delta_run.reserve(run.size())); HIPCHK(c, c->delta_status.reserve(n));
-    HIPCHK(c, hipMemcpyAsync(c->deltas.p, sorted.data(), n * sizeof(nhdfit_delta), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->delta_run.p, run.data(), run.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->deltas.p, sorted.data(), n * sizeof(nhdfit_delta), hipMemcpyHostToDevice, c->streams.use(0)));
+    HIPCHK(c, hipMemcpyAsync(c->delta_run.p, run.data(), run.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->streams.use(0)));
     DeltaArgs da;
     memset(&da, 0, sizeof da);
     da.p0 = c->p0.p; da.p1 = c->p1.p; da.p2 = c->p2.p; da.p3 = c->p3.p; da.p4 = c->p4.p; da.det = c->det.p; da.origin = c->origin.p;
     da.deltas = c->deltas.p; da.run = c->delta_run.p; da.n_runs = n_runs; da.sigs = sig_table(c); da.status = c->delta_status.p;
-    LAUNCH(c, k_delta, dim3((n_runs + 63) / 64), dim3(64), 0, c->stream, da);
+    hipLaunchKernelGGL(k_delta, dim3((n_runs + 63) / 64), dim3(64), 0, c->streams.use(0), da);
     HIPCHK(c, hipGetLastError());
     std::vector<uint8_t> st(n);
-    HIPCHK(c, hipMemcpyAsync(st.data(), c->delta_status.p, n, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, wait_stream(c->stream));                  // (also keeps `sorted` / `run` alive until the copies are done)
+    HIPCHK(c, hipMemcpyAsync(st.data(), c->delta_status.p, n, hipMemcpyDeviceToHost, c->streams.use(0)));
+    HIPCHK(c, c->streams.wait(0));                  // (also keeps `sorted` / `run` alive until the copies are done)
     for (uint32_t i = 0; i < n; ++i) status_out[order[i]] = st[i];
     if (c->rec_lo == c->rec_hi) { c->rec_lo = lo; c->rec_hi = hi; }
     else { c->rec_lo = std::min(c->rec_lo, lo); c->rec_hi = std::max(c->rec_hi, hi); }
@@ -2572,7 +2547,7 @@ int nhdfit_download_nodes(nhdfit_ctx* c, uint32_t first, uint32_t count, nhdfit_
     if (!c) return NHDFIT_E_INVAL;
     if ((uint64_t)first + count > c->n) return fail(c, NHDFIT_E_INVAL, "download [%u,%u) exceeds the %u nodes of the mirror", first, first + count, c->n);
     HIPCHK(c, hipSetDevice(c->dev));
-    HIPCHK(c, wait_stream(c->stream));
+    HIPCHK(c, c->streams.wait(0));
     if (p0) HIPCHK(c, hipMemcpy(p0, c->p0.p + first, count * sizeof *p0, hipMemcpyDeviceToHost));
     if (p1) HIPCHK(c, hipMemcpy(p1, c->p1.p + first, count * sizeof *p1, hipMemcpyDeviceToHost));
     if (p2) HIPCHK(c, hipMemcpy(p2, c->p2.p + first, count * sizeof *p2, hipMemcpyDeviceToHost));
@@ -2586,8 +2561,7 @@ int nhdfit_set_outputs(nhdfit_ctx* c, int want_bitmap, int want_map) {
     if (!c) return NHDFIT_E_INVAL;
     if ((want_bitmap != 0) != c->want_bitmap || (want_map != 0) != c->want_map) {   // steps in flight keep the old setting
         HIPCHK(c, hipSetDevice(c->dev));
-        int rc_ = sync_all(c);
-        if (rc_) return rc_;
+        TRY(sync_all(c));
     }
     c->want_bitmap = want_bitmap != 0;
     c->want_map = want_map != 0;
@@ -2624,7 +2598,7 @@ int nhdfit_comm_init(nhdfit_ctx* c, int nranks, int rank, const void* id128) {
 int nhdfit_comm_destroy(nhdfit_ctx* c) {
     if (!c) return NHDFIT_E_INVAL;
     if (c->comm) {
-        { int rc_ = sync_all(c); if (rc_) return rc_; }
+        TRY(sync_all(c));
         g_rccl.CommDestroy(c->comm);
         c->comm = nullptr;
     }
@@ -2657,14 +2631,16 @@ int nhdfit_comm_sendrecv(nhdfit_ctx* c, const void* send_buf, size_t send_bytes,
     // communicator in call order (the same order on every rank)
     HIPCHK(c, c->xfer_send.reserve(send_bytes ? send_bytes : 1));
     HIPCHK(c, c->xfer_recv.reserve(recv_bytes ? recv_bytes : 1));
-    if (sending) HIPCHK(c, hipMemcpyAsync(c->xfer_send.p, send_buf, send_bytes, hipMemcpyHostToDevice, c->s_red));
-    ncclResult_t r = g_rccl.GroupStart();
-    if (r == ncclSuccess && sending) r = (c->known_idle = false, g_rccl).Send(c->xfer_send.p, send_bytes, ncclUint8, dst, c->comm, c->s_red);
-    if (r == ncclSuccess && receiving) r = (c->known_idle = false, g_rccl).Recv(c->xfer_recv.p, recv_bytes, ncclUint8, src, c->comm, c->s_red);
+    if (sending) HIPCHK(c, hipMemcpyAsync(c->xfer_send.p, send_buf, send_bytes, hipMemcpyHostToDevice, c->streams.use(kRed)));
+    const ncclResult_t r = g_rccl.GroupStart();
+    int rc = r == ncclSuccess ? NHDFIT_OK : fail(c, NHDFIT_E_RCCL, "ncclGroupStart: %s", g_rccl.GetErrorString(r));
+    if (!rc && sending) rc = rccl(c, kRed, "ncclSend", &Rccl::Send, c->xfer_send.p, send_bytes, ncclUint8, dst, c->comm);
+    if (!rc && receiving) rc = rccl(c, kRed, "ncclRecv", &Rccl::Recv, c->xfer_recv.p, recv_bytes, ncclUint8, src, c->comm);
     const ncclResult_t r2 = g_rccl.GroupEnd();
-    if (r != ncclSuccess || r2 != ncclSuccess) return fail(c, NHDFIT_E_RCCL, "ncclSend / ncclRecv: %s", g_rccl.GetErrorString(r != ncclSuccess ? r : r2));
-    if (receiving) HIPCHK(c, hipMemcpyAsync(recv_buf, c->xfer_recv.p, recv_bytes, hipMemcpyDeviceToHost, c->s_red));
-    HIPCHK(c, wait_stream(c->s_red));
+    if (rc) return rc;
+    if (r2 != ncclSuccess) return fail(c, NHDFIT_E_RCCL, "ncclSend / ncclRecv: %s", g_rccl.GetErrorString(r2));
+    if (receiving) HIPCHK(c, hipMemcpyAsync(recv_buf, c->xfer_recv.p, recv_bytes, hipMemcpyDeviceToHost, c->streams.use(kRed)));
+    HIPCHK(c, c->streams.wait(kRed));
     return NHDFIT_OK;
 }
 
@@ -2674,11 +2650,10 @@ int nhdfit_comm_allreduce_sum_u8(nhdfit_ctx* c, void* buf, size_t bytes) {
     if (!buf) return fail(c, NHDFIT_E_INVAL, "allreduce: no buffer");
     HIPCHK(c, hipSetDevice(c->dev));
     HIPCHK(c, c->xfer_send.reserve(bytes));
-    HIPCHK(c, hipMemcpyAsync(c->xfer_send.p, buf, bytes, hipMemcpyHostToDevice, c->s_red));
-    ncclResult_t r = (c->known_idle = false, g_rccl).AllReduce(c->xfer_send.p, c->xfer_send.p, bytes, ncclUint8, ncclSum, c->comm, c->s_red);
-    if (r != ncclSuccess) return fail(c, NHDFIT_E_RCCL, "ncclAllReduce(uint8, sum): %s", g_rccl.GetErrorString(r));
-    HIPCHK(c, hipMemcpyAsync(buf, c->xfer_send.p, bytes, hipMemcpyDeviceToHost, c->s_red));
-    HIPCHK(c, wait_stream(c->s_red));
+    HIPCHK(c, hipMemcpyAsync(c->xfer_send.p, buf, bytes, hipMemcpyHostToDevice, c->streams.use(kRed)));
+    TRY(rccl(c, kRed, "ncclAllReduce(uint8, sum)", &Rccl::AllReduce, c->xfer_send.p, c->xfer_send.p, bytes, ncclUint8, ncclSum, c->comm));
+    HIPCHK(c, hipMemcpyAsync(buf, c->xfer_send.p, bytes, hipMemcpyDeviceToHost, c->streams.use(kRed)));
+    HIPCHK(c, c->streams.wait(kRed));
     return NHDFIT_OK;
 }
 
@@ -2749,17 +2724,19 @@ int nhdfit_group_find(nhdfit_group* g, const nhdfit_req* reqs, uint32_t P, doubl
     std::vector<std::vector<uint64_t>> host_scores;
     if (!g->comm.empty()) {
         ncclResult_t r = g_rccl.GroupStart();
-        for (size_t k = 0; k < n && r == ncclSuccess; ++k) {
+        int rc = NHDFIT_OK;
+        for (size_t k = 0; k < n && r == ncclSuccess && !rc; ++k) {
             nhdfit_ctx* c = g->ctx[k];
             Pipe& p = c->pipe[0];                                        // (a freshly staged batch's one step runs on pipe 0)
             if (hipSetDevice(c->dev) != hipSuccess) { r = ncclSystemError; break; }
             const int b = p.n_fit ? (int)((p.n_fit - 1) % kBufs) : 0;
             if (!c->n) {                                                 // a shard without nodes contributes "no feasible node"
-                if (p.score[b].reserve(P) != hipSuccess || hipMemsetAsync(p.score[b].p, 0, (size_t)P * 8, c->stream) != hipSuccess) { r = ncclSystemError; break; }
+                if (p.score[b].reserve(P) != hipSuccess || hipMemsetAsync(p.score[b].p, 0, (size_t)P * 8, c->streams.use(0)) != hipSuccess) { r = ncclSystemError; break; }
             }
-            r = (c->known_idle = false, g_rccl).AllReduce(p.score[b].p, p.score[b].p, P, ncclUint64, ncclMax, g->comm[k], c->stream);
+            if ((rc = rccl(c, 0, "ncclAllReduce (group)", &Rccl::AllReduce, p.score[b].p, p.score[b].p, P, ncclUint64, ncclMax, g->comm[k]))) g->err = c->err;
         }
         ncclResult_t r2 = g_rccl.GroupEnd();
+        if (rc) return rc;
         if (r != ncclSuccess || r2 != ncclSuccess) { g->err = std::string("ncclAllReduce (group): ") + g_rccl.GetErrorString(r != ncclSuccess ? r : r2); return NHDFIT_E_RCCL; }
     } else if (n > 1) {                                                  // host max-reduce (debug / test path): D2H, max, H2D
         host_scores.resize(n);
@@ -2769,7 +2746,7 @@ int nhdfit_group_find(nhdfit_group* g, const nhdfit_req* reqs, uint32_t P, doubl
             if (!c->n) continue;
             Pipe& p = c->pipe[0];
             HIPCHK(c, hipSetDevice(c->dev));
-            HIPCHK(c, wait_stream(c->stream));
+            HIPCHK(c, c->streams.wait(0));
             const int b = (int)((p.n_fit - 1) % kBufs);
             HIPCHK(c, hipMemcpy(tmp.data(), p.score[b].p, (size_t)P * 8, hipMemcpyDeviceToHost));
             for (uint32_t i = 0; i < P; ++i) best[i] = std::max(best[i], tmp[i]);
@@ -2819,43 +2796,43 @@ int explain_run(nhdfit_ctx* c, DevBuf<R>& dreqs, const R* reqs, uint32_t P, doub
     if ((P + kExplainPods - 1) / kExplainPods > 65535u) return fail(c, NHDFIT_E_LIMIT, "%u requests in one explain call (<= %u)", P, 65535u * kExplainPods);
     if (c->n && !c->ncls) return fail(c, NHDFIT_E_STATE, "set the dictionary first (nhdfit_set_dictionary: the NIC capacity classes)");
     HIPCHK(c, hipSetDevice(c->dev));
-    { int rc_ = sync_all(c); if (rc_) return rc_; }             // (the mirror as the last call left it)
+    TRY(sync_all(c));             // (the mirror as the last call left it)
     const uint32_t n = c->n;
     const size_t chunks = (n + 63) / 64;
     HIPCHK(c, dreqs.reserve(P));
     HIPCHK(c, c->ex_counts.reserve((size_t)P * NHDFIT_STAGES));
     HIPCHK(c, c->ex_flags.reserve(1));
-    HIPCHK(c, hipMemcpyAsync(dreqs.p, reqs, (size_t)P * sizeof *reqs, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->ex_counts.p, 0, (size_t)P * NHDFIT_STAGES * sizeof(uint32_t), c->stream));
-    HIPCHK(c, hipMemsetAsync(c->ex_flags.p, 0, sizeof(uint32_t), c->stream));
+    HIPCHK(c, hipMemcpyAsync(dreqs.p, reqs, (size_t)P * sizeof *reqs, hipMemcpyHostToDevice, c->streams.use(0)));
+    HIPCHK(c, hipMemsetAsync(c->ex_counts.p, 0, (size_t)P * NHDFIT_STAGES * sizeof(uint32_t), c->streams.use(0)));
+    HIPCHK(c, hipMemsetAsync(c->ex_flags.p, 0, sizeof(uint32_t), c->streams.use(0)));
     if (n) {
         HIPCHK(c, c->ex_views.reserve(n));
         HIPCHK(c, c->ex_slot.reserve(n));
         if (stage_out) HIPCHK(c, c->ex_stage.reserve((size_t)P * n));
         if (cand) {
             HIPCHK(c, c->ex_cand.reserve(chunks));
-            HIPCHK(c, hipMemcpyAsync(c->ex_cand.p, cand, chunks * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, hipMemcpyAsync(c->ex_cand.p, cand, chunks * sizeof(uint64_t), hipMemcpyHostToDevice, c->streams.use(0)));
         }
         ExplainViewArgs va;
         memset(&va, 0, sizeof va);
         va.p0 = c->p0.p; va.p1 = c->p1.p; va.p2 = c->p2.p; va.p3 = c->p3.p; va.p4 = c->p4.p; va.det = c->det.p; va.n = n;
         va.wide = c->wide.p; va.n_wide = c->n_wide; va.views = c->ex_views.p; va.slot = c->ex_slot.p;
-        LAUNCH(c, k_explain_views, dim3((n + kExplainThreads - 1) / kExplainThreads), dim3(kExplainThreads), 0, c->stream, va);
+        hipLaunchKernelGGL(k_explain_views, dim3((n + kExplainThreads - 1) / kExplainThreads), dim3(kExplainThreads), 0, c->streams.use(0), va);
         HIPCHK(c, hipGetLastError());
         ExplainArgs<R> ea;
         memset(&ea, 0, sizeof ea);
         ea.views = c->ex_views.p; ea.slot = c->ex_slot.p; ea.n = n; ea.wide = c->wide.p; ea.share = c->sharing ? c->wide_share.p : nullptr;
         ea.reqs = dreqs.p; ea.P = P; ea.caps = c->caps.p; ea.busy_from = busy_threshold(now); ea.cand = cand ? c->ex_cand.p : nullptr;
         ea.budget = budget; ea.counts = c->ex_counts.p; ea.stage = stage_out ? c->ex_stage.p : nullptr; ea.flags = c->ex_flags.p;
-        LAUNCH(c, k_explain<R>, dim3((n + kExplainThreads - 1) / kExplainThreads, (P + kExplainPods - 1) / kExplainPods), dim3(kExplainThreads), 0,
-               c->stream, ea);
+        hipLaunchKernelGGL(k_explain<R>, dim3((n + kExplainThreads - 1) / kExplainThreads, (P + kExplainPods - 1) / kExplainPods), dim3(kExplainThreads), 0,
+               c->streams.use(0), ea);
         HIPCHK(c, hipGetLastError());
-        if (stage_out) HIPCHK(c, hipMemcpyAsync(stage_out, c->ex_stage.p, (size_t)P * n, hipMemcpyDeviceToHost, c->stream));
+        if (stage_out) HIPCHK(c, hipMemcpyAsync(stage_out, c->ex_stage.p, (size_t)P * n, hipMemcpyDeviceToHost, c->streams.use(0)));
     }
     uint32_t fl = 0;
-    HIPCHK(c, hipMemcpyAsync(counts_out, c->ex_counts.p, (size_t)P * NHDFIT_STAGES * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(&fl, c->ex_flags.p, sizeof fl, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, wait_stream(c->stream));
+    HIPCHK(c, hipMemcpyAsync(counts_out, c->ex_counts.p, (size_t)P * NHDFIT_STAGES * sizeof(uint32_t), hipMemcpyDeviceToHost, c->streams.use(0)));
+    HIPCHK(c, hipMemcpyAsync(&fl, c->ex_flags.p, sizeof fl, hipMemcpyDeviceToHost, c->streams.use(0)));
+    HIPCHK(c, c->streams.wait(0));
     if (fl) return fail(c, NHDFIT_E_LIMIT, "a big request's NIC stage ran out of search budget on some node (%u steps per NIC question, pod and node)", budget);
     return NHDFIT_OK;
 }
@@ -2890,8 +2867,7 @@ int nhdfit_get_stats(nhdfit_ctx* c, nhdfit_stats* out) {
     if (!c || !out) return NHDFIT_E_INVAL;
     if (c->ev_pending) {                                    // sampled launches whose events have not been read yet (waits for them if need be)
         HIPCHK(c, hipSetDevice(c->dev));
-        int rc = drain_events(c);
-        if (rc) return rc;
+        TRY(drain_events(c));
     }
     *out = c->stats;
     return NHDFIT_OK;

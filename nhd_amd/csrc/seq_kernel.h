@@ -571,9 +571,4 @@ struct CommitArgs {
     uint32_t node; nhdfit_req req; nhdfit_mapping map; double busy_time; SigTable sigs; CommitHost* host; uint32_t seq;
     uint32_t ncls;                 // capacity classes of the dictionary (the wavefront form's signature keys)
 };
-__device__ __forceinline__ void commit_publish(CommitHost* h, const nhdfit_placement& pl, uint32_t seq) {
-    h->place = pl;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __hip_atomic_store(&h->flag, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
 // (k_commit itself: seq2_kernel.h, behind the wavefront form of the commit step)
