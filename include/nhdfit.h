@@ -477,6 +477,24 @@ int nhdfit_schedule_batch(nhdfit_ctx* ctx, const nhdfit_req* reqs, uint32_t P, d
 int nhdfit_commit(nhdfit_ctx* ctx, uint32_t node, const nhdfit_req* req, const nhdfit_mapping* map, double busy_time,
                   nhdfit_placement* place_out);
 
+/* FindNode for ONE pod and, if a node is found, the commit step on it (nhd/NHDScheduler.py:277-304) in one call.
+ * score_out / map_out as nhdfit_find; place_out as nhdfit_commit (valid when the winner lies in this context's shard);
+ * *committed = 1 when the mirror now holds the placement.
+ * prev_node (local index, -1: none) / prev_busy_time: one correction, "as if a NHDFIT_DELTA_SET_BUSY for that node had been
+ * applied before this call" - the busy time the scheduler's SetBusy wrote after the PREVIOUS call, which is later than the one that
+ * call committed (nhd/Node.py:843-845), without a blocking nhdfit_apply_deltas per pod.
+ * One launch when the lone-pod form of the find applies (no communicator, no wide record in the mirror, at most three
+ * processing groups, a dictionary that fits the block's LDS, mapping output on); otherwise, and when that launch reports a commit
+ * the reference would raise on, the call composes the correction, nhdfit_find and nhdfit_commit itself: the same answer, the old
+ * cost.  With a communicator the find runs its all-reduce; only the rank that owns the winner commits and fills place_out.  A
+ * mirror that holds wide records is refused (NHDFIT_E_STATE): compose nhdfit_find and nhdfit_wide_commit. */
+int nhdfit_find_commit(nhdfit_ctx* ctx, const nhdfit_req* req, double now, const uint64_t* cand, double busy_time,
+                       int64_t prev_node, double prev_busy_time,
+                       uint64_t* score_out, nhdfit_mapping* map_out, nhdfit_placement* place_out, int* committed);
+/* how many nhdfit_find_commit calls took the one-launch form / the composed form since the context was created (a call
+ * that finds no node counts by the form it took; a launch that reports "found, not committed" counts as composed) */
+int nhdfit_find_commit_counts(nhdfit_ctx* ctx, uint64_t* fused, uint64_t* composed);
+
 /* Benchmark / pipelined form: requests are staged once, then each step only enqueues kernels
  * (request digest -> fit_score -> [all-reduce] -> winner mapping) on the context's stream. */
 int nhdfit_stage_requests(nhdfit_ctx* ctx, const nhdfit_req* reqs, uint32_t P);

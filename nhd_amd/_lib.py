@@ -45,6 +45,8 @@ _SIGS = {
     "nhdfit_schedule_batch": (c_int, [c_void_p, c_void_p, c_uint32, c_double, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                       POINTER(c_uint32)]),
     "nhdfit_commit": (c_int, [c_void_p, c_uint32, c_void_p, c_void_p, c_double, c_void_p]),
+    "nhdfit_find_commit": (c_int, [c_void_p, c_void_p, c_double, c_void_p, c_double, ctypes.c_int64, c_double, c_void_p, c_void_p, c_void_p, POINTER(c_int)]),
+    "nhdfit_find_commit_counts": (c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),
     "nhdfit_wide_upload": (c_int, [c_void_p, c_uint32, c_uint32, c_void_p, c_uint32]),
     "nhdfit_wide_share_upload": (c_int, [c_void_p, c_void_p, c_uint32]),
     "nhdfit_wide_share_download": (c_int, [c_void_p, c_void_p, c_uint32, POINTER(c_uint32)]),

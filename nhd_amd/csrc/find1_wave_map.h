@@ -42,11 +42,23 @@ __device__ __forceinline__ bool map_on_state_wave_small(const nhdfit_req& r, con
     if (!nic_ok) m = nhdfit_mapping{};
     return nic_ok;
 }
+// the staging area of the tail: the winner's planes 0-3 and its detail record, the capacity classes (a launch that goes on with the
+// winner - find1_commit.h - finds them here behind the mapping, and carves its own slices behind these)
+struct LoneMapLds { NodeState* st; nhdfit_detail* dd; double* caps; };
+__device__ __forceinline__ LoneMapLds lone_map_lds(uint8_t*& lds) {
+    LoneMapLds l;
+    l.st = carve<NodeState>(lds, 1);
+    l.dd = carve<nhdfit_detail>(lds, 1);
+    l.caps = carve<double>(lds, NHDFIT_MAX_CLASSES);
+    return l;
+}
+// `keep` (LDS, or null): the mapping is left there as well (zeros when nothing was mapped)
 __device__ __forceinline__ void map_lone_pod_wave(const MapArgs& a, const ShapeArgs& h, const LoneMasks& t, const nhdfit_req& r,
-                                                  const double* __restrict__ caps, uint8_t* lds) {
-    NodeState* st = carve<NodeState>(lds, 1);
-    nhdfit_detail* dd = carve<nhdfit_detail>(lds, 1);
-    double* l_caps = carve<double>(lds, NHDFIT_MAX_CLASSES);
+                                                  const double* __restrict__ caps, uint8_t* lds, nhdfit_mapping* keep) {
+    const LoneMapLds l = lone_map_lds(lds);
+    NodeState* st = l.st;
+    nhdfit_detail* dd = l.dd;
+    double* l_caps = l.caps;
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     if (tid < 64u) {                                                      // wavefront 0; the others wait at the barrier below
         nhdfit_mapping mp = nhdfit_mapping{};
@@ -74,6 +86,7 @@ __device__ __forceinline__ void map_lone_pod_wave(const MapArgs& a, const ShapeA
             map_on_state_wave_small(r, *st, *dd, l_caps, bits, mt, lane, mp);   // every lane: the same mapping (zeros when nothing fits)
         }
         if (lane == 0u && r.n_groups <= 3u) a.out[0] = mp;                // (a pod with four groups is mapped by k_map<true>, as before)
+        if (keep && lane == 0u) *keep = mp;
     }
     __syncthreads();
 }

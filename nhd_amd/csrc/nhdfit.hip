@@ -60,6 +60,7 @@ namespace {
 #include "seq_kernel.h"
 #include "find1_wave_map.h"
 #include "seq2_kernel.h"
+#include "find1_commit.h"
 #include "wide_kernel.h"
 #include "big_kernel.h"
 #include "explain_kernel.h"
@@ -262,6 +263,7 @@ struct nhdfit_ctx {
     DevBuf<uint32_t> find_sync;
     DevBuf<unsigned long long> find_red;   // sharded single-launch find: the tile's scores on their way through the all-reduce
     uint32_t find_seq = 0;
+    uint64_t fc_fused = 0, fc_composed = 0;   // nhdfit_find_commit calls by the form they took (nhdfit_find_commit_counts)
     std::vector<uint64_t> cand_shadow;   // copy of the mask a small find last uploaded to `cand` (empty: unknown)
     bool fast_find = tune_env("NHDFIT_NO_FAST_FIND") == nullptr;   // tuning aid: every find through the staged five-launch path
     // single-launch find of a whole batch (k_findn): its host block (flag | scores | mappings, grown with the largest call), its counters
@@ -641,6 +643,7 @@ int nhdfit_set_dictionary(nhdfit_ctx* c, uint32_t max_cores_per_numa, uint32_t m
     HIPCHK(c, hipFuncSetAttribute((const void*)k_step<512>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     HIPCHK(c, hipFuncSetAttribute((const void*)k_find<256>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     HIPCHK(c, hipFuncSetAttribute((const void*)k_find1<256>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    HIPCHK(c, hipFuncSetAttribute((const void*)k_find1_commit<256>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     HIPCHK(c, hipFuncSetAttribute((const void*)k_step<256>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     HIPCHK(c, hipFuncSetAttribute((const void*)k_step<512, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     HIPCHK(c, hipFuncSetAttribute((const void*)k_step<256, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
@@ -1546,6 +1549,42 @@ int nhdfit_fetch(nhdfit_ctx* c, uint64_t* score_out, uint64_t* bitmap_out, nhdfi
 }
 
 namespace {
+// the arguments of the lone-pod launch (k_find1 / k_find1_commit): the request is in the host block, c->use_cand says whether a mask is up
+Find1Args lone_find_args(nhdfit_ctx* c, double now, uint32_t seq, bool want_map) {
+    Pipe& p = c->pipe[0];
+    FindHost* h = c->find_host;
+    const uint32_t chunks = (c->n + 63) / 64;
+    Find1Args a1;
+    memset(&a1, 0, sizeof a1);
+    a1.m = make_map_args(c, p, 0);
+    a1.m.reqs = h->reqs; a1.m.tile_wcls = nullptr; a1.m.tabs = nullptr; a1.m.out = h->maps; a1.m.P = 1;
+    a1.m.score = reinterpret_cast<const unsigned long long*>(c->find_sync.p + 4);
+    a1.h = make_shape_args(c, p, 0);
+    a1.p4 = c->p4.p;
+    a1.d = DictView{c->caps.p, c->ncls, c->group_sets.p, SigDict{c->sig_off.p, c->pool_off.p, c->pool_glimit.p, c->cc.p, c->nsig}, c->sig_flat.p, c->flat_words, nullptr, 0};
+    a1.nsig = c->nsig; a1.fc_dim = c->max_cores + 1; a1.fg_dim = c->max_gpus + 1; a1.ngs = c->ngs;
+    a1.chunks = chunks;
+    static const uint32_t lone_nb = tune_env("NHDFIT_FIND_BLOCKS") ? (uint32_t)atoi(tune_env("NHDFIT_FIND_BLOCKS")) : 0u;   // tuning aid
+    a1.nb = std::max(1u, std::min(chunks, lone_nb ? lone_nb : std::min((chunks + 7) / 8, (uint32_t)c->prop.multiProcessorCount)));   // two chunks per wavefront
+    a1.busy_from = busy_threshold(now);
+    a1.cand = c->use_cand ? c->cand.p : nullptr;
+    a1.sync = c->find_sync.p; a1.host = h; a1.seq = seq; a1.want_map = want_map ? 1u : 0u;
+    return a1;
+}
+// the candidate mask of a small find: uploaded when it differs from the one that is up (consecutive pods of one node group come with
+// the same mask)
+hipError_t upload_small_cand(nhdfit_ctx* c, const uint64_t* cand) {
+    const uint32_t chunks = (c->n + 63) / 64;
+    c->use_cand = cand != nullptr;
+    hipError_t e = hipSuccess;
+    if (cand && (c->cand_shadow.size() != chunks || c->cand.cap < chunks || memcmp(c->cand_shadow.data(), cand, (size_t)chunks * 8) != 0)) {
+        c->cand_shadow.clear();
+        e = c->cand.reserve(chunks);
+        if (e == hipSuccess) e = hipMemcpyAsync(c->cand.p, cand, (size_t)chunks * 8, hipMemcpyHostToDevice, c->streams.use(0));
+        if (e == hipSuccess) c->cand_shadow.assign(cand, cand + chunks);
+    }
+    return e;
+}
 // nhdfit_find for at most one pod tile and no verdict matrix - the scheduler's pod-at-a-time FindNode - as ONE launch (k_find,
 // step_kernel.h): the requests are read from, and the results stored into, a fine-grained host block; the host polls the
 // sequence word the launch stores last.  Returns 1 when the call is not eligible (or the launch gave up): the caller then
@@ -1584,14 +1623,7 @@ int find_small(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, double now, co
     if (e == hipSuccess) e = p.score[0].reserve(kTile);
     const uint32_t chunks = (c->n + 63) / 64;
     c->use_cand = cand != nullptr;
-    if (e == hipSuccess && cand && (c->cand_shadow.size() != chunks || c->cand.cap < chunks ||
-                                    memcmp(c->cand_shadow.data(), cand, (size_t)chunks * 8) != 0)) {
-        // (consecutive pods of one node group come with the same mask: it is uploaded when it changes)
-        c->cand_shadow.clear();
-        e = c->cand.reserve(chunks);
-        if (e == hipSuccess) e = hipMemcpyAsync(c->cand.p, cand, (size_t)chunks * 8, hipMemcpyHostToDevice, c->streams.use(0));
-        if (e == hipSuccess) c->cand_shadow.assign(cand, cand + chunks);
-    }
+    if (e == hipSuccess) e = upload_small_cand(c, cand);
     if (e != hipSuccess) { c->P = 0; return fail(c, NHDFIT_E_HIP, "small find: %s", hipGetErrorString(e)); }
 
     FindHost* h = c->find_host;
@@ -1600,21 +1632,7 @@ int find_small(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, double now, co
     if (seq == 0u || seq == kFindAborted) seq = c->find_seq = 1u;
     Find1Args a1;
     memset(&a1, 0, sizeof a1);
-    if (lone) {
-        a1.m = make_map_args(c, p, 0);
-        a1.m.reqs = h->reqs; a1.m.tile_wcls = nullptr; a1.m.tabs = nullptr; a1.m.out = h->maps;
-        a1.m.score = reinterpret_cast<const unsigned long long*>(c->find_sync.p + 4);
-        a1.h = make_shape_args(c, p, 0);
-        a1.p4 = c->p4.p;
-        a1.d = DictView{c->caps.p, c->ncls, c->group_sets.p, SigDict{c->sig_off.p, c->pool_off.p, c->pool_glimit.p, c->cc.p, c->nsig}, c->sig_flat.p, c->flat_words, nullptr, 0};
-        a1.nsig = c->nsig; a1.fc_dim = c->max_cores + 1; a1.fg_dim = c->max_gpus + 1; a1.ngs = c->ngs;
-        a1.chunks = chunks;
-        static const uint32_t lone_nb = tune_env("NHDFIT_FIND_BLOCKS") ? (uint32_t)atoi(tune_env("NHDFIT_FIND_BLOCKS")) : 0u;   // tuning aid
-        a1.nb = std::max(1u, std::min(chunks, lone_nb ? lone_nb : std::min((chunks + 7) / 8, (uint32_t)c->prop.multiProcessorCount)));   // two chunks per wavefront
-        a1.busy_from = busy_threshold(now);
-        a1.cand = c->use_cand ? c->cand.p : nullptr;
-        a1.sync = c->find_sync.p; a1.host = h; a1.seq = seq; a1.want_map = map_out ? 1u : 0u;
-    }
+    if (lone) a1 = lone_find_args(c, now, seq, map_out != nullptr);
     FindArgs a;
     memset(&a, 0, sizeof a);
     a.s.shapes_P = P;
@@ -1701,6 +1719,93 @@ int find_small(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, double now, co
     c->stats.bytes_last = (uint64_t)c->n * 24ull + (uint64_t)P * sizeof(nhdfit_req) + (uint64_t)P * 8ull;
     c->stats.nodes = c->n; c->stats.nsig = c->nsig; c->stats.ncls = c->ncls; c->stats.lds_bytes = c->lds_bytes;
     c->stats.small_finds++;
+    return NHDFIT_OK;
+}
+
+// nhdfit_find_commit as ONE launch (k_find1_commit, find1_commit.h) when the lone-pod form of the find applies: the conditions are the
+// ones find_small tests for a lone pod, and no communicator (the winner of a sharded find is known only behind the all-reduce).
+// Returns 0 = done; 1 = not eligible, nothing launched, nothing touched; 2 = launched, a node was found and mapped (score_out / map_out
+// are filled, the correction is in the mirror) but NOT committed - the caller finishes with nhdfit_commit; < 0 = error (worded).
+SigTable sig_table(nhdfit_ctx* c);
+int find_commit_fused(nhdfit_ctx* c, const nhdfit_req* req, double now, const uint64_t* cand, double busy_time, int64_t prev_node,
+                      double prev_busy_time, uint64_t* score_out, nhdfit_mapping* map_out, nhdfit_placement* place_out, int* committed) {
+    if (!c->fast_find || !c->lone_pod || !c->nsig || !c->n || !c->find_host || c->n_wide || c->comm || !c->want_map) return 1;
+    if (req->hugepages_gb < 0 || req->hugepages_gb > kMaxHpRows - 2) return 1;
+    if (req_valid(*req) && req->n_groups > 3) return 1;         // the generic set model is a kernel of its own
+    if (!c->flat_words || c->flat_words > kDictLdsWords || c->nsig > kLoneMaxSigs) return 1;
+    const auto t0 = std::chrono::steady_clock::now();
+    HIPCHK(c, hipSetDevice(c->dev));
+    // the launch writes the planes: the writer's rule of nhdfit_commit - steps in flight on either pipe read them, so wait for every
+    // stream, unless nothing can be in flight anywhere but on this very stream
+    if (c->P || !c->streams.sides_clean()) {
+        TRY(sync_all(c));
+        TRY(drain_events(c));
+    } else TRY(check_skipped_waits(c, "nhdfit_find_commit"));
+    Pipe& p = c->pipe[0];
+    for (Pipe& q : c->pipe) q.n_dig = q.n_fit = q.n_shaped = q.n_chosen = q.n_finished = 0;
+    c->n_enq = 0; c->last_pipe = 0; c->n_items = 0; c->n_big_pods = 0;
+    c->P = 0;                                                   // nothing is (or stays) staged
+    c->hp_rows = (uint32_t)req->hugepages_gb + 2;
+    c->max_wcls = req_valid(*req) ? wclass_of(req->n_groups) : 0;
+    hipError_t e = p.score[0].reserve(kTile);
+    if (e == hipSuccess) e = upload_small_cand(c, cand);
+    if (e != hipSuccess) return fail(c, NHDFIT_E_HIP, "find and commit: %s", hipGetErrorString(e));
+    FindHost* h = c->find_host;
+    h->reqs[0] = *req;
+    h->committed = 0;
+    uint32_t seq = ++c->find_seq;
+    if (seq == 0u || seq == kFindAborted) seq = c->find_seq = 1u;
+    Find1CommitArgs a;
+    memset(&a, 0, sizeof a);
+    a.f = lone_find_args(c, now, seq, true);
+    a.p0 = c->p0.p; a.p1 = c->p1.p; a.p2 = c->p2.p; a.p3 = c->p3.p; a.p4 = c->p4.p; a.det = c->det.p;
+    a.sigs = sig_table(c); a.ncls = c->ncls;
+    a.busy_time = busy_time;
+    a.prev_node = prev_node < 0 ? kNoPrevNode : (uint32_t)prev_node; a.prev_busy_time = prev_busy_time;
+    const bool clocks = kTuning && c->role_step >= 0;           // tuning aid (NHDFIT_ROLE_TIMES): the phases of the launch on the device clock
+    constexpr int kSlots = kClockCommitTail + 1;
+    if (clocks) {
+        HIPCHK(c, c->role_clock.reserve(2 * kSlots));
+        unsigned long long init[2 * kSlots];
+        for (int k = 0; k < kSlots; ++k) { init[2 * k] = ~0ull; init[2 * k + 1] = 0; }
+        HIPCHK(c, hipMemcpy(c->role_clock.p, init, sizeof init, hipMemcpyHostToDevice));
+        a.f.role_clock = c->role_clock.p;
+    }
+    const auto t_launch = std::chrono::steady_clock::now();
+    hipLaunchKernelGGL((k_find1_commit<256>), dim3(a.f.nb), dim3(256), kLoneLds + map_tile_lds_bytes<256>(), c->streams.use(0), a);
+    HIPCHK(c, hipGetLastError());
+    uint32_t seen = 0;
+    TRY(poll_word(c, &h->flag, seq, seq, t_launch, 500, 0, seen));
+    if (seen != seq) return fail(c, NHDFIT_E_HIP, "the find-and-commit kernel ended without publishing its results");
+    if (clocks) {
+        const double us_seen = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_launch).count();
+        unsigned long long t[2 * kSlots];
+        HIPCHK(c, c->streams.wait(0));
+        HIPCHK(c, hipMemcpy(t, c->role_clock.p, sizeof t, hipMemcpyDeviceToHost));
+        unsigned long long first = ~0ull;
+        for (int k = 0; k < kSlots; ++k) first = t[2 * k] < first ? t[2 * k] : first;
+        static const char* names[kSlots] = {"choose", "shapes", "finish", "digest", "fit", "commit"};
+        fprintf(stderr, "[nhdfit] find and commit in one launch: %u blocks, results seen %.1f us after the launch call began (host prep %.1f us)\n", a.f.nb, us_seen,
+                std::chrono::duration<double, std::micro>(t_launch - t0).count());
+        for (int k = 0; k < kSlots; ++k)
+            if (t[2 * k + 1]) fprintf(stderr, "[nhdfit]   %-6s: +%.2f us .. +%.2f us\n", names[k], (t[2 * k] - first) * 0.01, (t[2 * k + 1] - first) * 0.01);
+    }
+    *score_out = h->score[0];
+    *map_out = h->maps[0];
+    c->stats.evals_last = c->n;
+    c->stats.bytes_last = (uint64_t)c->n * 24ull + sizeof(nhdfit_req) + 8ull;
+    c->stats.nodes = c->n; c->stats.nsig = c->nsig; c->stats.ncls = c->ncls; c->stats.lds_bytes = c->lds_bytes;
+    if (prev_node >= 0) {                                       // the correction wrote plane 4 of that node
+        const uint32_t v = (uint32_t)prev_node;
+        if (c->rec_lo == c->rec_hi) { c->rec_lo = v; c->rec_hi = v + 1; }
+        else { c->rec_lo = std::min(c->rec_lo, v); c->rec_hi = std::max(c->rec_hi, v + 1); }
+    }
+    if (!h->committed) return h->score[0] && h->maps[0].valid ? 2 : NHDFIT_OK;
+    *place_out = h->place;
+    *committed = 1;
+    const uint32_t node = (uint32_t)(NHDFIT_SCORE_INDEX(h->score[0]) - c->global_base);
+    if (c->rec_lo == c->rec_hi) { c->rec_lo = node; c->rec_hi = node + 1; }
+    else { c->rec_lo = std::min(c->rec_lo, node); c->rec_hi = std::max(c->rec_hi, node + 1); }
     return NHDFIT_OK;
 }
 
@@ -2479,6 +2584,49 @@ int nhdfit_commit(nhdfit_ctx* c, uint32_t node, const nhdfit_req* req, const nhd
     *place_out = c->commit_host->place;
     if (c->rec_lo == c->rec_hi) { c->rec_lo = node; c->rec_hi = node + 1; }
     else { c->rec_lo = std::min(c->rec_lo, node); c->rec_hi = std::max(c->rec_hi, node + 1); }
+    return NHDFIT_OK;
+}
+
+int nhdfit_find_commit(nhdfit_ctx* c, const nhdfit_req* req, double now, const uint64_t* cand, double busy_time,
+                       int64_t prev_node, double prev_busy_time,
+                       uint64_t* score_out, nhdfit_mapping* map_out, nhdfit_placement* place_out, int* committed) {
+    if (!c || !req || !score_out || !map_out || !place_out || !committed) return NHDFIT_E_INVAL;
+    if (prev_node < -1 || prev_node >= (int64_t)c->n) return fail(c, NHDFIT_E_INVAL, "prev_node %lld out of range (%u nodes; -1: none)", (long long)prev_node, c->n);
+    *committed = 0;
+    *score_out = 0;
+    memset(map_out, 0, sizeof *map_out);
+    memset(place_out, 0, sizeof *place_out);
+    if (c->n_wide) return fail(c, NHDFIT_E_STATE, "the mirror holds %u wide node(s): their commit step is nhdfit_wide_commit - compose nhdfit_find with it", c->n_wide);
+    if (!c->want_map) return fail(c, NHDFIT_E_STATE, "the mapping output is off (nhdfit_set_outputs): the commit step needs the winner's mapping");
+    const int rf = find_commit_fused(c, req, now, cand, busy_time, prev_node, prev_busy_time, score_out, map_out, place_out, committed);
+    if (rf < 0) return rf;
+    if (rf == 0) { c->fc_fused++; return NHDFIT_OK; }
+    // The composed form: the correction, nhdfit_find's own path, nhdfit_commit's - the same answer at the old cost.
+    c->fc_composed++;
+    if (rf == 1 && prev_node >= 0) {                            // (rf == 2: the launch has stored it)
+        HIPCHK(c, hipSetDevice(c->dev));
+        // a writer of the mirror: as nhdfit_commit
+        if (c->P || !c->streams.sides_clean()) TRY(sync_all(c));
+        else TRY(check_skipped_waits(c, "nhdfit_find_commit"));
+        hipLaunchKernelGGL(k_set_busy, dim3(1), dim3(64), 0, c->streams.use(0), c->p4.p, (uint32_t)prev_node, prev_busy_time);   // (stream order: the find follows on pipe 0)
+        HIPCHK(c, hipGetLastError());
+        const uint32_t v = (uint32_t)prev_node;
+        if (c->rec_lo == c->rec_hi) { c->rec_lo = v; c->rec_hi = v + 1; }
+        else { c->rec_lo = std::min(c->rec_lo, v); c->rec_hi = std::max(c->rec_hi, v + 1); }
+    }
+    if (rf == 1) TRY(nhdfit_find(c, req, 1, now, cand, score_out, nullptr, map_out));
+    if (!*score_out || !map_out->valid) return NHDFIT_OK;       // nothing fits (or, sharded, another rank owns the winner's mapping)
+    const uint64_t gi = NHDFIT_SCORE_INDEX(*score_out);
+    if (gi < c->global_base || gi >= c->global_base + c->n) return NHDFIT_OK;       // sharded: the rank that owns the winner commits
+    TRY(nhdfit_commit(c, (uint32_t)(gi - c->global_base), req, map_out, busy_time, place_out));
+    *committed = 1;
+    return NHDFIT_OK;
+}
+
+int nhdfit_find_commit_counts(nhdfit_ctx* c, uint64_t* fused, uint64_t* composed) {
+    if (!c || !fused || !composed) return NHDFIT_E_INVAL;
+    *fused = c->fc_fused;
+    *composed = c->fc_composed;
     return NHDFIT_OK;
 }
 

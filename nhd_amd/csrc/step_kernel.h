@@ -376,6 +376,9 @@ struct FindHost {                                    // one per context, hipHost
     unsigned long long score[kTile];                 // out
     nhdfit_mapping maps[kTile];                      // out
     nhdfit_req reqs[kTile];                          // in
+    nhdfit_placement place;                          // out, k_find1_commit (find1_commit.h): the placement record of the commit in the launch's tail
+    uint32_t committed;                              // out, k_find1_commit: 1 = the mirror holds the placement; 0 = nothing found, or "found, not committed"
+    uint32_t pad2[3];
 };
 constexpr uint32_t kFindAborted = 0xFFFFFFFFu;
 constexpr uint32_t kFindSpinLimit = 1u << 16;
@@ -544,9 +547,18 @@ constexpr size_t kLoneLds = lds_slice(sizeof(nhdfit_req)) + lds_slice(sizeof(Pod
                             2 * lds_slice(2 * kLoneCoreDim * 2 * sizeof(uint16_t)) + lds_slice(kDictLdsWords * sizeof(uint16_t)) +
                             2 * lds_slice(kLoneMaxSigs * sizeof(uint16_t)) + lds_slice(8 * sizeof(unsigned long long));
 __device__ __forceinline__ void map_lone_pod_wave(const MapArgs& a, const ShapeArgs& h, const LoneMasks& t, const nhdfit_req& r,
-                                                  const double* __restrict__ caps, uint8_t* lds);      // find1_wave_map.h, behind seq_kernel.h
-template <int BLOCK>
-__global__ __launch_bounds__(BLOCK) void k_find1(Find1Args a) {
+                                                  const double* __restrict__ caps, uint8_t* lds, nhdfit_mapping* keep);   // find1_wave_map.h, behind seq_kernel.h
+// What a launch of this form does beyond the find is its TAIL: none for nhdfit_find (k_find1 below); the commit step on the winner for
+// nhdfit_find_commit (find1_commit.h, behind seq2_kernel.h: the wavefront form of the commit is defined there).  A tail says which busy
+// time the sweep reads for a node (the caller's correction for one node) and what the block with the last ticket does behind the mapping.
+struct Find1NoTail {
+    static constexpr bool kCommits = false;
+    __device__ __forceinline__ double busy_time(uint32_t, double stored) const { return stored; }
+    __device__ __forceinline__ nhdfit_mapping* kept_mapping(uint8_t*) const { return nullptr; }
+    __device__ __forceinline__ void run(const Find1Args&, const nhdfit_req&, uint8_t*) const {}
+};
+template <int BLOCK, class TAIL>
+__device__ __forceinline__ void find1_launch(const Find1Args& a, const TAIL& tail) {
     extern __shared__ __align__(16) uint8_t lds_all[];
     uint8_t* lds = lds_all;
     nhdfit_req* s_req = carve<nhdfit_req>(lds, 1);
@@ -617,7 +629,7 @@ __global__ __launch_bounds__(BLOCK) void k_find1(Find1Args a) {
         if (i < a.m.n) {
             const NodeIdx ni = node_index(a.m.p0[i], a.m.p1[i], a.m.p2[i], a.p4[i], a.fc_dim, a.fg_dim, a.ngs);
             nogpu = ni.nogpu != 0;
-            ok = lone_pod_fits(t, h, ni, a.m.p3[i], a.p4[i].busy_time >= a.busy_from, a.d.group_sets);
+            ok = lone_pod_fits(t, h, ni, a.m.p3[i], tail.busy_time(i, a.p4[i].busy_time) >= a.busy_from, a.d.group_sets);
             if (a.cand && !(a.cand[c] >> lane & 1)) ok = false;
         }
         const uint64_t word = __ballot(ok), pref = needs_gpu ? 0ull : word & __ballot(nogpu);
@@ -653,8 +665,9 @@ __global__ __launch_bounds__(BLOCK) void k_find1(Find1Args a) {
         m.reqs = s_req;                                                   // the request is in this block's LDS already: no second read of the host block
         // one wavefront, the lanes working together (find1_wave_map.h; round 5: -3 us per call against the tile machinery with one
         // live lane, profiles/r05/candidates.md); stores the mapping into the host block
-        map_lone_pod_wave(m, a.h, t, *s_req, a.d.caps, lds_map);
+        map_lone_pod_wave(m, a.h, t, *s_req, a.d.caps, lds_map, tail.kept_mapping(lds_map));
         stamp(a.role_clock, 2, t2);
+        if constexpr (TAIL::kCommits) tail.run(a, *s_req, lds_map);       // (the winner's state and the mapping are in this block's LDS)
     }
     if (tid == 0) a.host->score[0] = __hip_atomic_load(a.m.score, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     NHDFIT_DRAIN_VMEM();                                                  // every wave's stores into the host block, then the word behind them
@@ -665,3 +678,5 @@ __global__ __launch_bounds__(BLOCK) void k_find1(Find1Args a) {
         __hip_atomic_store(&a.host->flag, a.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
 }
+template <int BLOCK>
+__global__ __launch_bounds__(BLOCK) void k_find1(Find1Args a) { find1_launch<BLOCK>(a, Find1NoTail{}); }

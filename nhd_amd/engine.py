@@ -2,7 +2,7 @@
 from __future__ import annotations
 
 import ctypes
-from typing import Optional
+from typing import Optional, Tuple
 
 import numpy as np
 
@@ -251,6 +251,30 @@ class Engine:
         mapping = np.ascontiguousarray(mapping)
         self._chk(self.lib.nhdfit_commit(self.ctx, int(node), _p(req), _p(mapping), float(busy_time), _p(out)))
         return out
+
+    def find_commit(self, req: np.ndarray, now: float, busy_time: float, cand: Optional[np.ndarray] = None, prev: Optional[Tuple[int, float]] = None):
+        """FindNode for ONE pod and the commit step on its winner in one call (nhdfit_find_commit; one launch where the lone-pod form
+        of the find applies): (score, mapping, placement, committed).  `req`: one pack.REQ record; `prev` = (local node index, busy
+        time): as if a SET_BUSY delta for that node had been applied first."""
+        req = np.ascontiguousarray(req).reshape(-1)[:1]
+        score = np.zeros(1, np.uint64)
+        maps = np.zeros(1, pack.MAPPING)
+        place = np.zeros((), pack.PLACEMENT)
+        done = ctypes.c_int(0)
+        if cand is not None:
+            cand = np.ascontiguousarray(cand, dtype=np.uint64)
+            assert cand.shape == ((self.n + 63) // 64,)
+        pn, pt = (-1, 0.0) if prev is None else (int(prev[0]), float(prev[1]))
+        self._chk(self.lib.nhdfit_find_commit(self.ctx, _p(req), float(now), _p(cand), float(busy_time), pn, pt, _p(score), _p(maps), _p(place),
+                                              ctypes.byref(done)))
+        self.P = 1
+        return int(score[0]), maps[0], place, bool(done.value)
+
+    def find_commit_counts(self) -> Tuple[int, int]:
+        """(fused, composed): find_commit calls of this context by the form they took (nhdfit_find_commit_counts)."""
+        f, c = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        self._chk(self.lib.nhdfit_find_commit_counts(self.ctx, ctypes.byref(f), ctypes.byref(c)))
+        return int(f.value), int(c.value)
 
     # ---- pods with 5..8 processing groups: the general path over every node (nhdfit_big_find / nhdfit_big_commit) --------
     def big_find(self, reqs: np.ndarray, now: float, cand: Optional[np.ndarray] = None, want_map=True):
@@ -610,6 +634,20 @@ class GroupEngine:
     def wide_commit(self, node: int, req, mapping, busy_time):
         k = self._shard_of(node)
         return self.shards[k].wide_commit(node - self._bounds[k][0], req, mapping, busy_time)
+
+    def find_commit(self, req: np.ndarray, now: float, busy_time: float, cand: Optional[np.ndarray] = None, prev: Optional[Tuple[int, float]] = None):
+        """Engine.find_commit over the shards (node indices global): the group's find, then the commit on the context that owns the
+        winner - composed by nature, the winner is known only behind the all-reduce.  `prev` travels as a SET_BUSY delta to its owner."""
+        req = np.ascontiguousarray(req).reshape(-1)[:1]
+        if prev is not None:
+            d = np.zeros(1, pack.DELTA)
+            d["node"], d["op"], d["busy_time"] = int(prev[0]), pack.DELTA_SET_BUSY, float(prev[1])
+            self.apply_deltas(d)
+        score, _, maps = self.find(req, now, cand=cand, want_bitmap=False, want_map=True)
+        s = int(score[0])
+        if not s or not int(maps[0]["valid"]):
+            return s, maps[0], np.zeros((), pack.PLACEMENT), False
+        return s, maps[0], self.commit(winner_index(s), req[0], maps[0], busy_time), True
 
     def big_find(self, reqs: np.ndarray, now: float, cand: Optional[np.ndarray] = None, want_map=True):
         """Big requests over every shard: each device runs the general pass on its nodes (nhdfit_big_find), the score words -

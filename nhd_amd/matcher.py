@@ -19,7 +19,8 @@ Two ways to keep the device mirror current:
   accepts any subset ``nl`` of ``nodes`` in the same relative order (what InitialNodeFilter
   produces, nhd/NHDScheduler.py:235-247) and turns it into a candidate bitmask.
 
-``FindNodes(nl, tops, pod_groups)`` is the batch form (every pod against one snapshot).
+``FindNodes(nl, tops, pod_groups)`` is the batch form (every pod against one snapshot).  ``ScheduleOne(nl, top)`` is FindNode
+and the commit step on the winner in one device call (attached mode: the scheduler's own mutators then find the mirror current).
 """
 from __future__ import annotations
 
@@ -202,6 +203,9 @@ class HipMatcher:
         self._claims: Dict[str, frozenset] = {}
         self._batch_ids: Dict[str, list] = {}              # ScheduleBatch(apply=True): ids the device already committed, per node, in order
         self._deltas: List[np.ndarray] = []                # release / reclaim / reset / SetHugepages waiting for the device, in call order
+        # ScheduleOne: (winner, busy time committed on the device, its ids) of the last call - what the scheduler's SetBusy writes
+        # behind it is recognised by these (_on_commit), and a later time rides in the next ScheduleOne instead of a delta of its own
+        self._one: Optional[Tuple[str, float, dict]] = None
         self.delta_stats = {"applied": 0, "repacked": 0}
         self._uploaded_ids: Optional[Tuple[int, ...]] = None
         # candidate masks of the filtered dicts seen lately, by (length, first, middle, last name) -> [(names, mask)]: pods of a few
@@ -355,6 +359,10 @@ class HipMatcher:
         # committed earlier inside a batch carried the batch's `now` - the busy time SetBusy wrote since (time.monotonic(),
         # nhd/Node.py:843-845) then follows as a delta of its own
         carried = set() if from_batch else {"busy_time", "SetBusy"}
+        one = self._one
+        if from_batch and one is not None and one[2] is ids and float(node.busy_time) == one[1]:
+            carried = {"busy_time", "SetBusy"}                 # ScheduleOne committed this very time (a scheduler on a virtual clock, or one
+                                                               # that hands its SetBusy time in): nothing left to send
         left = self._reasons.get(node.name, set()) - carried
         if left:
             self._reasons[node.name] = left                    # cordon / maintenance / groups written earlier still go out as deltas
@@ -530,6 +538,114 @@ class HipMatcher:
         commits in the device mirror (attached mode: the reference mutators that follow are then recognised as
         already mirrored); apply=False restores it."""
         return self._run(nl, tops, pod_groups, now, sequential=True, apply=apply)
+
+    def ScheduleOne(self, nl: Dict[str, object], top, pod_groups: Optional[Sequence[str]] = None, now: Optional[float] = None,
+                    busy_time: Optional[float] = None) -> Tuple:
+        """FindNode for one pod AND the commit step on its winner in the device mirror, in one device call (nhdfit_find_commit: one
+        launch where the lone-pod form of the find applies).  Returns what FindNode returns - `(name, mapping)` or `(None,)`; the
+        contract is ScheduleBatch(apply=True)'s with one pod: `self.last_placements == [ids]`, the node objects are NOT touched, and
+        in attached mode the scheduler's own SetBusy / SetPhysicalIdsFromMapping / ClaimPodNICResources that follow
+        (nhd/NHDScheduler.py:289-304) find their work mirrored already; a placement the caller never applies makes the node re-pack
+        from its object before the next call.  `busy_time`: what the commit writes as the node's busy time; with `now` and
+        `busy_time` both left out ONE reading of the clock serves as both, given alone each is used as given and the other read from
+        the clock.  The time SetBusy writes afterwards does not go out as a delta of its own: equal to the committed one it is
+        dropped, otherwise it rides in the next ScheduleOne (any other call flushes it as an ordinary SET_BUSY delta first).
+        Pods of the general path, mirrors with wide nodes, ENABLE_SHARING and engines without find_commit are composed from
+        FindNodes + CommitPlacement: the same answer."""
+        try:
+            return self._schedule_one(nl, top, pod_groups, now, busy_time)
+        except NhdFitError as e:
+            if self.strict:
+                raise
+            self.logger.error("ScheduleOne: the device path failed (%s): the pod is answered (None,)", e)
+            self._mirror_foreign = True                   # whatever the mirror holds now, rebuild it before the next call
+            self._last_subset = None
+            self._one = None
+            self.last_placements = [None]
+            return (None,)
+
+    _BUSY_REASONS = frozenset(("busy_time", "SetBusy"))
+
+    def _schedule_one(self, nl, top, pod_groups, now, busy_time) -> Tuple:
+        if len(top.proc_groups) == 0 and len(nl):
+            raise IndexError("pod without processing groups (the reference fails the same way, Matcher.py:346)")
+        self.last_placements = [None]
+        if len(nl) == 0:
+            return (None,)
+        if now is None and busy_time is None:
+            now = busy_time = self.clock()
+        else:
+            now = self.clock() if now is None else now
+            busy_time = self.clock() if busy_time is None else busy_time
+        groups = None if pod_groups is None else [pod_groups]
+        one, self._one = self._one, None
+        if self._attached is None:                         # stateless: every call packs `nl` again - ScheduleBatch's path serves it
+            return self._run_checked(nl, [top], groups, now, sequential=True, apply=True)[0]
+        if not hasattr(self.engine, "find_commit") or pack.needs_general_path(top) or self.packer.sharing or (self._table is not None and self._table.wide):
+            return self._schedule_one_composed(nl, top, groups, now, busy_time)
+        # the one pending correction: the last winner, dirty for nothing but the time SetBusy wrote behind the commit
+        late = None
+        if one is not None and one[0] in self._dirty and one[0] not in self._batch_ids and self._reasons.get(one[0], {""}) <= self._BUSY_REASONS:
+            late = self._dirty.pop(one[0])
+            self._reasons.pop(one[0], None)
+        cand = self._sync_mirror(nl)
+        beyond: List[Tuple[int, str]] = []
+        reqs = self.packer.digest_many([top], groups, unsupported=beyond)
+        if beyond or self._mirror_foreign or self.packer.sharing or self._table.wide:
+            if late is not None:
+                self._mark(late, "busy_time")              # (travels as a delta after all)
+            if beyond:
+                self.logger.error("the pod cannot be expressed as a request record and is answered (None,): %s", beyond[0][1])
+                return (None,)
+            return self._schedule_one_composed(nl, top, groups, now, busy_time)
+        prev = None
+        if late is not None and late.name in self._index and not self._off_planes(late.name):
+            prev = (self._index[late.name], float(late.busy_time))
+        self.packer.close_signatures()                     # every NIC state a commit can produce has a signature
+        self.engine.set_dictionary(self.packer)
+        score, mp, place, done = self.engine.find_commit(reqs[0], now, busy_time, cand=cand, prev=prev)
+        if not score:
+            return (None,)
+        i = winner_index(score) - self.engine.global_base
+        name = self._names[i]
+        gpu, cpu, nic_numa, nic_idx, valid = pack.unpack_mappings(mp.reshape(1))[0]
+        if not valid or not done:
+            raise RuntimeError(f"internal error: no mapping / no commit produced for feasible node {name}")
+        status = int(place["status"])
+        if status == pack.COMMIT_NEW_SIG:                  # cannot happen after close_signatures(); handled anyway (CommitPlacement)
+            fix = self.engine.download(i, 1)
+            sn, sp = self.packer.sigs_from_detail(fix.detail[0])
+            fix.p3[0]["sig_numa"], fix.p3[0]["sig_pci"] = sn, sp
+            self.engine.set_dictionary(self.packer)
+            self.engine.upload(fix, first=i, capacity=len(self._names))
+        elif status == pack.COMMIT_WOULD_RAISE:
+            self.logger.warning("ScheduleOne: the reference's commit step would have failed on node %s", name)
+        G = int(reqs[0]["n_groups"])
+        nd = self._attached.get(name)
+        if nd is not None:
+            cpp = int(nd.cores_per_proc)
+            ids = pack.expand_placement(place, G, cpp, cpp * int(nd.sockets), [int(reqs[0]["gpus"][g]) for g in range(G)])
+            self.last_placements = [ids]
+            self._batch_ids.setdefault(name, []).append(ids)    # the reference mutators that follow find their work mirrored already
+            self._one = (name, float(busy_time), ids)
+        return (name, {"gpu": gpu[:G], "cpu": cpu[:G + 1], "nic": list(zip(nic_numa[:G], nic_idx[:G]))})
+
+    def _schedule_one_composed(self, nl, top, groups, now, busy_time) -> Tuple:
+        """ScheduleOne from the existing methods: FindNodes' path, then CommitPlacement on the winner."""
+        r = self._run_checked(nl, [top], groups, now, sequential=False)[0]
+        self.last_placements = [None]
+        if r[0] is None:
+            return r
+        if self._mirror_foreign or r[0] not in self._attached:     # `nl` is not (part of) the attached dict: as the stateless form
+            return self._run_checked(nl, [top], groups, now, sequential=True, apply=True)[0]
+        ids = self.CommitPlacement(r[0], top, r[1], busy_time=busy_time)
+        self.last_placements = [ids]
+        if self._off_planes(r[0]):                         # a wide record is re-packed from the object before the next call (no delta form)
+            self._mark(self._attached[r[0]], "wide-batch")
+        else:
+            self._batch_ids.setdefault(r[0], []).append(ids)
+            self._one = (r[0], float(busy_time), ids)
+        return r
 
     def FindNodes(self, nl: Dict[str, object], tops: Sequence[object],
                   pod_groups: Optional[Sequence[Sequence[str]]] = None, now: Optional[float] = None) -> List[Tuple]:

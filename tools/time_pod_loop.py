@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """The scheduler's pod-at-a-time loop through the drop-in class (bench.py sched_loop, leg pod_by_pod_kernel_filter), call by call:
 FindNodes([top], pod_groups) and CommitPlacement timed separately, then the C-ABI calls under them alone (nhdfit_find with one
-pod, nhdfit_commit), at BASELINE config 4's node mix.   tools/time_pod_loop.py [nodes] [pods]"""
+pod, nhdfit_commit), at BASELINE config 4's node mix; then the one-call form on the same inputs: Engine.find_commit alone
+(nhdfit_find_commit) and HipMatcher.ScheduleOne per pod.   tools/time_pod_loop.py [nodes] [pods]"""
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -62,4 +63,32 @@ for rq in reqs:
 out["abi_find_between_commits_us"] = tf / len(reqs) * 1e6
 out["abi_commit_us"] = tc / max(done, 1) * 1e6
 out["abi_commits"] = done
+# the same two steps as ONE call (nhdfit_find_commit), on the mirror as it stands now, with the next pods of the list
+reqs1 = [m.packer.digest_many([t], [g]) for t, g in zip(tops[200:400], groups[200:400])] or reqs
+f0, c0 = eng.find_commit_counts()
+t0 = time.perf_counter()
+done = 0
+for rq in reqs1:
+    done += eng.find_commit(rq[0], now, now)[3]
+out["abi_find_commit_us"] = (time.perf_counter() - t0) / len(reqs1) * 1e6
+out["abi_find_commits"] = done
+f1, c1 = eng.find_commit_counts()
+out["abi_find_commit_fused"], out["abi_find_commit_composed"] = f1 - f0, c1 - c0
+eng.close()
+# ... and through the drop-in class: ScheduleOne per pod (the loop of the first leg with one call in place of two)
+for rep in range(2):
+    nodes = spec.build_nodes()
+    m = HipMatcher(clock=lambda: now)
+    m.attach(nodes)
+    placed = 0
+    t_all = time.perf_counter()
+    for k, top in enumerate(tops):
+        r = m.ScheduleOne(nodes, top, pod_groups=groups[k], now=now, busy_time=now)
+        placed += r[0] is not None
+        m._batch_ids.clear()        # (as the first leg: the node objects are not brought along - the scheduler's mutators would consume these)
+    t_all = time.perf_counter() - t_all
+    out["scheduleone_loop_us_per_pod"] = t_all / P * 1e6
+    out["scheduleone_placed"] = placed
+    out["scheduleone_fused"], out["scheduleone_composed"] = m.engine.find_commit_counts()
+    m.engine.close()
 print(json.dumps(out))
