@@ -572,6 +572,44 @@ int nhdfit_explain_big(nhdfit_ctx* ctx, const nhdfit_big_req* reqs, uint32_t P, 
 int nhdfit_group_explain(nhdfit_group* g, const nhdfit_req* reqs, uint32_t P, double now, const uint64_t* const* cand,
                          uint32_t* counts_out, uint8_t* const* stage_out);
 
+/* ---- headroom: how many more replicas of a pod each node can take -----------------------------------------------------
+ * For a pod template and a node, the number of times the scheduler's own per-pod sequence succeeds back to back on a private
+ * copy of the node, with the busy window out of the way (capacity, not rate: the call takes no `now`):
+ *     FindNode on the one node (nhd/NHDScheduler.py:277, IsBusy() false)  ->  SetPhysicalIdsFromMapping (:292, nhd/Node.py:663-841)
+ *     ->  ClaimPodNICResources (:302-304, nhd/Node.py:644-646)  ->  again, until FindNode returns (None,) or max_per_node is reached.
+ * Every replica meets the state the one before left (cores taken by GetFreeCpuBatch's walk, nhd/Node.py:502-519; a NIC claimed
+ * whole; a GPU gone from behind a PCIe switch, nhd/Node.py:648-655; hugepages, :794-796), so this is not free resources over demand.
+ * Nodes outside `cand`, nodes InitialNodeFilter drops (NHDFIT_RF_INITIAL_FILTER, nhd/NHDScheduler.py:235-247) and nodes in
+ * maintenance (nhd/Matcher.py:72) have headroom 0.  A commit only changes its own node, so the sum over the nodes is the number of
+ * replicas the scheduler's first-fit loop places once busy windows have passed.  Nothing is written: not the mirror, not the busy
+ * times, not the staged batch, not nhdfit_get_stats.
+ * Per node, a 16-bit entry: */
+#define NHDFIT_HEADROOM_COUNT_MASK    0x3FFFu   /* replicas, saturating at max_per_node (1..16383)                              */
+#define NHDFIT_HEADROOM_STOPPED       0x4000u   /* the run ended at a commit the reference raises on (IndexError / None out of
+                                                   SetPhysicalIdsFromMapping, nhd/Node.py:686) or at a NIC state without a signature
+                                                   in the dictionary: the count is what succeeded before it                       */
+#define NHDFIT_HEADROOM_NOT_EVALUATED 0x8000u   /* a candidate held as a wide record (ENABLE_SHARING mirrors: every node): no figure */
+#define NHDFIT_HEADROOM_FORM_WAVE     1u        /* the wavefront instantiation answered (templates of 1..3 processing groups)       */
+#define NHDFIT_HEADROOM_FORM_GENERIC  2u        /* the instantiation with the generic set model (four processing groups)           */
+typedef struct {
+    uint64_t replicas;                          /* sum of the counts                                                               */
+    uint32_t nodes_with_room;                   /* nodes with a count >= 1                                                         */
+    uint32_t max_on_one_node;
+    uint32_t saturated;                         /* nodes that reached max_per_node                                                 */
+    uint32_t stopped;                           /* nodes flagged NHDFIT_HEADROOM_STOPPED                                           */
+    uint32_t not_evaluated;                     /* nodes flagged NHDFIT_HEADROOM_NOT_EVALUATED                                     */
+    uint32_t form;                              /* NHDFIT_HEADROOM_FORM_*; 0: nothing was launched (an empty mirror)               */
+} nhdfit_headroom_sum;                          /* 32 bytes */
+/* sum_out [P]; counts_out: NULL, or [P][n] entries by node index.  cand as nhdfit_find.  A request of an invalid map type fits
+ * nowhere (all zero), as nhdfit_find answers it.  nhdfit_big_req pods have no entry here.  NHDFIT_E_LIMIT: a dictionary whose
+ * signature stream does not fit the block's LDS (more than 4096 NIC signatures), a hugepage request beyond the pod tile's. */
+int nhdfit_headroom(nhdfit_ctx* ctx, const nhdfit_req* reqs, uint32_t P, const uint64_t* cand, uint32_t max_per_node,
+                    nhdfit_headroom_sum* sum_out, uint16_t* counts_out);
+/* ... over every shard of a group: sum_out summed over the devices (max_on_one_node: the largest); counts_out NULL, or one
+ * [P][shard's n] buffer (or NULL) per shard.  cand as nhdfit_group_find. */
+int nhdfit_group_headroom(nhdfit_group* g, const nhdfit_req* reqs, uint32_t P, const uint64_t* const* cand, uint32_t max_per_node,
+                          nhdfit_headroom_sum* sum_out, uint16_t* const* counts_out);
+
 /* ---- request digest straight from the wire format (host code, no GPU needed) -------------------------
  * The pod's Triad libconfig text -> nhdfit_req, replacing TriadCfgParser(text, False).CfgToTopology(False)
  * (nhd/TriadCfgParser.py:337-380, called from nhd/NHDScheduler.py:262-270) followed by the getters FindNode

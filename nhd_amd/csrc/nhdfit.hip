@@ -64,6 +64,7 @@ namespace {
 #include "wide_kernel.h"
 #include "big_kernel.h"
 #include "explain_kernel.h"
+#include "headroom_kernel.h"
 
 // ------------------------------------------------------------------------------------------------
 // host side
@@ -287,6 +288,8 @@ struct nhdfit_ctx {
     // nhdfit_explain / nhdfit_explain_big (explain_kernel.h): buffers of their own - an explanation leaves the staged batch alone
     DevBuf<nhdfit_wide_node> ex_views; DevBuf<int32_t> ex_slot; DevBuf<nhdfit_req> ex_reqs; DevBuf<nhdfit_big_req> ex_big_reqs;
     DevBuf<uint32_t> ex_counts, ex_flags; DevBuf<uint64_t> ex_cand; DevBuf<uint8_t> ex_stage;
+    // nhdfit_headroom (headroom_kernel.h): buffers of its own as well
+    DevBuf<nhdfit_req> hr_reqs; DevBuf<uint32_t> hr_tickets; DevBuf<HeadroomSum> hr_sum; DevBuf<uint16_t> hr_counts; DevBuf<uint64_t> hr_cand;
     int wide_slot(uint32_t node) const {
         auto it = std::lower_bound(wide_index.begin(), wide_index.end(), node);
         return it != wide_index.end() && *it == node ? (int)(it - wide_index.begin()) : -1;
@@ -508,6 +511,7 @@ void nhdfit_destroy(nhdfit_ctx* c) {
     c->big_cand.release(); c->big_scratch.release();
     c->ex_views.release(); c->ex_slot.release(); c->ex_reqs.release(); c->ex_big_reqs.release(); c->ex_counts.release(); c->ex_flags.release();
     c->ex_cand.release(); c->ex_stage.release();
+    c->hr_reqs.release(); c->hr_tickets.release(); c->hr_sum.release(); c->hr_counts.release(); c->hr_cand.release();
     if (c->find_host) (void)hipHostFree(c->find_host);
     if (c->commit_host) (void)hipHostFree(c->commit_host);
     c->commit_host = nullptr;
@@ -3007,6 +3011,96 @@ int nhdfit_group_explain(nhdfit_group* g, const nhdfit_req* reqs, uint32_t P, do
         const int rc = nhdfit_explain(c, reqs, P, now, cand ? cand[k] : nullptr, part.data(), stage_out ? stage_out[k] : nullptr);
         if (rc) { g->err = c->err; return rc; }
         for (size_t j = 0; j < part.size(); ++j) counts_out[j] += part[j];
+    }
+    return NHDFIT_OK;
+}
+
+// ---- headroom: how many more replicas of a pod template each node can take (headroom_kernel.h) ---------------------------------------
+int nhdfit_headroom(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, const uint64_t* cand, uint32_t max_per_node, nhdfit_headroom_sum* sum_out,
+                    uint16_t* counts_out) {
+    if (!c) return NHDFIT_E_INVAL;
+    if (!reqs || !P || !sum_out) return fail(c, NHDFIT_E_INVAL, "headroom: requests and sum_out are required");
+    if (!max_per_node || max_per_node > NHDFIT_HEADROOM_COUNT_MASK)
+        return fail(c, NHDFIT_E_INVAL, "headroom: max_per_node is %u (1 .. %u)", max_per_node, (unsigned)NHDFIT_HEADROOM_COUNT_MASK);
+    if (P > 65535u) return fail(c, NHDFIT_E_LIMIT, "%u templates in one headroom call (<= 65535)", P);
+    for (uint32_t p = 0; p < P; ++p)
+        if (reqs[p].hugepages_gb > kMaxHpRows - 2) return fail(c, NHDFIT_E_LIMIT, "template %u asks for %d GB of hugepages (<= %d)", p, reqs[p].hugepages_gb, kMaxHpRows - 2);
+    memset(sum_out, 0, (size_t)P * sizeof *sum_out);
+    const uint32_t n = c->n;
+    if (!n) return NHDFIT_OK;
+    if (!c->ncls || !c->nsig) return fail(c, NHDFIT_E_STATE, "set the dictionary first (nhdfit_set_dictionary)");
+    if (!c->flat_words || c->flat_words > kDictLdsWords || c->nsig > kLoneMaxSigs)
+        return fail(c, NHDFIT_E_LIMIT, "headroom: the dictionary's signature stream (%u words, %u signatures) does not fit the block's LDS (%u words, %u signatures)",
+                    c->flat_words, c->nsig, kDictLdsWords, kLoneMaxSigs);
+    HIPCHK(c, hipSetDevice(c->dev));
+    TRY(sync_all(c));             // (the mirror as the last call left it; steps in flight are drained, their results stay fetchable)
+    const uint32_t chunks = (n + 63) / 64;
+    const size_t pitch = (size_t)chunks * 64;
+    HIPCHK(c, c->hr_reqs.reserve(P));
+    HIPCHK(c, c->hr_tickets.reserve(P));
+    HIPCHK(c, c->hr_sum.reserve(P));
+    HIPCHK(c, c->hr_counts.reserve((size_t)P * pitch));
+    HIPCHK(c, hipMemcpyAsync(c->hr_reqs.p, reqs, (size_t)P * sizeof *reqs, hipMemcpyHostToDevice, c->streams.use(0)));
+    HIPCHK(c, hipMemsetAsync(c->hr_tickets.p, 0, (size_t)P * sizeof(uint32_t), c->streams.use(0)));
+    HIPCHK(c, hipMemsetAsync(c->hr_sum.p, 0, (size_t)P * sizeof(HeadroomSum), c->streams.use(0)));
+    if (cand) {
+        HIPCHK(c, c->hr_cand.reserve(chunks));
+        HIPCHK(c, hipMemcpyAsync(c->hr_cand.p, cand, (size_t)chunks * sizeof(uint64_t), hipMemcpyHostToDevice, c->streams.use(0)));
+    }
+    HeadroomArgs a;
+    memset(&a, 0, sizeof a);
+    a.p0 = c->p0.p; a.p1 = c->p1.p; a.p2 = c->p2.p; a.p3 = c->p3.p; a.p4 = c->p4.p; a.det = c->det.p; a.n = n;
+    a.wide = c->wide.p; a.n_wide = c->n_wide;
+    a.reqs = c->hr_reqs.p;
+    a.d = DictView{c->caps.p, c->ncls, c->group_sets.p, SigDict{c->sig_off.p, c->pool_off.p, c->pool_glimit.p, c->cc.p, c->nsig}, c->sig_flat.p, c->flat_words, nullptr, 0};
+    a.nsig = c->nsig; a.fc_dim = c->max_cores + 1; a.fg_dim = c->max_gpus + 1; a.ngs = c->ngs;
+    const ShapeArgs sh = make_shape_args(c, c->pipe[0], 0);
+    a.mt = MapTables{sh.asc, sh.choose_tab, sh.st};
+    a.sigs = sig_table(c); a.ncls = c->ncls;
+    a.cand = cand ? c->hr_cand.p : nullptr;
+    a.chunks = chunks; a.cap = max_per_node;
+    a.tickets = c->hr_tickets.p; a.counts = c->hr_counts.p; a.sum = c->hr_sum.p;
+    a.all_generic = a.mt.choose_tab && a.mt.st.info ? 0u : 1u;
+    bool any_wave = false, any_g4 = false;
+    std::vector<uint32_t> form(P);
+    for (uint32_t p = 0; p < P; ++p) {
+        const bool g4 = a.all_generic || (req_valid(reqs[p]) && reqs[p].n_groups > 3);
+        form[p] = g4 ? NHDFIT_HEADROOM_FORM_GENERIC : NHDFIT_HEADROOM_FORM_WAVE;
+        (g4 ? any_g4 : any_wave) = true;
+    }
+    // blocks per template: the chip's block slots shared out among the templates, a chunk per block at the least
+    const uint32_t slots = 4u * (uint32_t)c->prop.multiProcessorCount;
+    const uint32_t nb = std::max(1u, std::min(chunks, (slots + P - 1) / P));
+    if (any_wave) hipLaunchKernelGGL(k_headroom<false>, dim3(nb, P), dim3(kHeadroomBlock), kHeadroomLds, c->streams.use(0), a);
+    HIPCHK(c, hipGetLastError());
+    if (any_g4) hipLaunchKernelGGL(k_headroom<true>, dim3(nb, P), dim3(kHeadroomBlock), kHeadroomLds, c->streams.use(0), a);
+    HIPCHK(c, hipGetLastError());
+    static_assert(sizeof(HeadroomSum) == sizeof(nhdfit_headroom_sum), "copied out as it is");
+    HIPCHK(c, hipMemcpyAsync(sum_out, c->hr_sum.p, (size_t)P * sizeof *sum_out, hipMemcpyDeviceToHost, c->streams.use(0)));
+    if (counts_out)
+        HIPCHK(c, hipMemcpy2DAsync(counts_out, (size_t)n * sizeof(uint16_t), c->hr_counts.p, pitch * sizeof(uint16_t), (size_t)n * sizeof(uint16_t), P,
+                                   hipMemcpyDeviceToHost, c->streams.use(0)));
+    HIPCHK(c, c->streams.wait(0));
+    for (uint32_t p = 0; p < P; ++p) sum_out[p].form = form[p];
+    return NHDFIT_OK;
+}
+
+int nhdfit_group_headroom(nhdfit_group* g, const nhdfit_req* reqs, uint32_t P, const uint64_t* const* cand, uint32_t max_per_node,
+                          nhdfit_headroom_sum* sum_out, uint16_t* const* counts_out) {
+    if (!g || !reqs || !P || !sum_out) return NHDFIT_E_INVAL;
+    std::vector<nhdfit_headroom_sum> part(P);
+    memset(sum_out, 0, (size_t)P * sizeof *sum_out);
+    for (size_t k = 0; k < g->ctx.size(); ++k) {
+        nhdfit_ctx* c = g->ctx[k];
+        const int rc = nhdfit_headroom(c, reqs, P, cand ? cand[k] : nullptr, max_per_node, part.data(), counts_out ? counts_out[k] : nullptr);
+        if (rc) { g->err = c->err; return rc; }
+        for (uint32_t p = 0; p < P; ++p) {
+            nhdfit_headroom_sum& s = sum_out[p];
+            s.replicas += part[p].replicas; s.nodes_with_room += part[p].nodes_with_room; s.saturated += part[p].saturated;
+            s.stopped += part[p].stopped; s.not_evaluated += part[p].not_evaluated;
+            s.max_on_one_node = std::max(s.max_on_one_node, part[p].max_on_one_node);
+            s.form = std::max(s.form, part[p].form);
+        }
     }
     return NHDFIT_OK;
 }

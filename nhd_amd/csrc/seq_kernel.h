@@ -158,7 +158,10 @@ __device__ __noinline__ uint32_t choose_model_cold(int G, int U, uint32_t sg, ui
 // map_on_state (seq_core.h) with the parallel pieces; every lane returns the same mapping
 // G4 = false: the caller knows that no pod of its batch has four processing groups - the generic set model (10 KB of private memory per
 // lane, reserved for every wavefront of a kernel that merely CONTAINS the call) is not compiled in (k_decide<false>, round 6)
-template <bool G4 = true>
+// COLD = false: the caller launches only where every shape of two NUMA nodes is answered from a table (MapTables complete) - the call
+// into the insertion-by-insertion model, whose frame every launch of a kernel that merely CONTAINS it reserves, is not compiled in.  A node
+// of ONE NUMA node needs neither: every tuple is all zeros, so each of the three sets holds that one tuple or nothing (k_headroom<false>)
+template <bool G4 = true, bool COLD = true>
 __device__ __forceinline__ bool map_on_state_wave(const nhdfit_req& r, const NodeState& s, const nhdfit_detail& d, const double* caps, uint32_t nic_bits,
                                                   const MapTables& t, uint32_t lane, nhdfit_mapping& m) {
     const WinnerState w = state_view(s, d, caps);
@@ -180,7 +183,9 @@ __device__ __forceinline__ bool map_on_state_wave(const nhdfit_req& r, const Nod
     uint32_t res;
     if (t.choose_tab && choose_tabulated(G, U)) res = choose_from_table(t.choose_tab, G, sg, sc, cd);
     else if (t.st.info && G == 3 && U == 2) res = choose_g3(t.st, t.asc, sg, sc, cd);
-    else res = choose_model_cold(G, U, sg, sc, cd, t.asc);
+    else if constexpr (COLD) res = choose_model_cold(G, U, sg, sc, cd, t.asc);
+    else if (U == 1) res = choose_result_word(true, 0u, 0);
+    else return false;
     if (!(res >> 8 & 1)) return false;
     const uint32_t gcode = (res >> 4) & 7u;
     const int ccode = (int)(res & 15u);

@@ -557,62 +557,71 @@ struct Find1NoTail {
     __device__ __forceinline__ nhdfit_mapping* kept_mapping(uint8_t*) const { return nullptr; }
     __device__ __forceinline__ void run(const Find1Args&, const nhdfit_req&, uint8_t*) const {}
 };
+// The launch's LDS in front of the tail's staging area (NHDFIT_LONE_LDS: carved off `lds`, which is left pointing behind it) and the pod's
+// masks derived into it (NHDFIT_LONE_POD_MASKS: every thread of the block; REQ = the pod's record in global or host memory; ends behind
+// a block barrier, with `r`, `valid`, `W` and `G` declared) - ONE text for every launch that answers for one pod against the nodes directly:
+// k_find1 and k_find1_commit below, k_headroom (headroom_kernel.h, one template per block).  Macros, not functions: pasted, the text
+// compiles in k_find1 to the machine code it always did (checked against the parent build when k_headroom arrived).
+#define NHDFIT_LONE_LDS(lds) \
+    nhdfit_req* s_req = carve<nhdfit_req>(lds, 1); \
+    PodSums* s_sum = carve<PodSums>(lds, 1); \
+    PodHeader* s_hdr = carve<PodHeader>(lds, 1); \
+    uint16_t* s_cover = carve<uint16_t>(lds, NHDFIT_MAX_CLASSES * (kMaxG + 1)); \
+    uint16_t* s_a0 = carve<uint16_t>(lds, kLoneGpuDim); \
+    uint16_t* s_a1 = carve<uint16_t>(lds, kLoneGpuDim); \
+    uint16_t* s_w0 = carve<uint16_t>(lds, 2 * kLoneCoreDim * 2); \
+    uint16_t* s_w1 = carve<uint16_t>(lds, 2 * kLoneCoreDim * 2); \
+    uint16_t* s_flat = carve<uint16_t>(lds, kDictLdsWords); \
+    uint16_t* s_r0 = carve<uint16_t>(lds, kLoneMaxSigs); \
+    uint16_t* s_r1 = carve<uint16_t>(lds, kLoneMaxSigs); \
+    unsigned long long* s_best = carve<unsigned long long>(lds, 8);
+#define NHDFIT_LONE_POD_MASKS(BLOCK, tid, REQ, D, NSIG, FC_DIM, FG_DIM) \
+    if (tid < sizeof(nhdfit_req) / 16) reinterpret_cast<uint4*>(s_req)[tid] = reinterpret_cast<const uint4*>((REQ))[tid]; \
+    for (uint32_t w = tid; w < (D).flat_words / 2; w += BLOCK)   /* (the stream is padded to an even word count) */ \
+        reinterpret_cast<uint32_t*>(s_flat)[w] = reinterpret_cast<const uint32_t*>((D).flat)[w]; \
+    __syncthreads(); \
+    const nhdfit_req& r = *s_req; \
+    const bool valid = req_valid(r); \
+    if (tid == 0) { \
+        *s_hdr = pod_header(r); \
+        s_sum->G = r.n_groups; s_sum->W = 1u << (r.n_groups & 7u); s_sum->full = s_sum->W - 1; \
+        s_sum->misc_smt = r.misc_smt; s_sum->misc_nosmt = r.misc_nosmt; \
+    } \
+    if (valid && tid < (1u << r.n_groups)) {   /* subset sums (pod_sums), one subset per thread */ \
+        uint32_t g = 0, x = 0, y = 0; \
+        for (uint32_t i = 0; i < r.n_groups; ++i) \
+            if (tid >> i & 1) { g += r.gpus[i]; x += r.cpu_smt[i]; y += r.cpu_nosmt[i]; } \
+        s_sum->gpu[tid] = g; s_sum->cpu_smt[tid] = x; s_sum->cpu_nosmt[tid] = y; \
+    } \
+    __syncthreads(); \
+    const uint32_t W = s_sum->W, G = s_sum->G; \
+    if (valid && tid < (D).ncls) class_cover(r, (D).caps[tid], W, G, &s_cover[tid * (kMaxG + 1)]); \
+    for (uint32_t k = tid; k < 2 * (FG_DIM); k += BLOCK) { \
+        const uint32_t u = k >= (FG_DIM), f = u ? k - (FG_DIM) : k; \
+        (u ? s_a1 : s_a0)[f] = valid ? (uint16_t)entry_a(*s_sum, u, f) : (uint16_t)0; \
+    } \
+    for (uint32_t k = tid; k < 2 * (2 * (FC_DIM) * 2); k += BLOCK) {   /* [u][smt * fc_dim + c][m] */ \
+        const uint32_t u = k >= 2 * (FC_DIM) * 2, e = u ? k - 2 * (FC_DIM) * 2 : k, m = e & 1, rec = e >> 1, smt = rec >= (FC_DIM), c = smt ? rec - (FC_DIM) : rec; \
+        (u ? s_w1 : s_w0)[e] = valid ? (uint16_t)entry_w(*s_sum, u, smt != 0, c, m) : (uint16_t)0; \
+    } \
+    __syncthreads(); \
+    for (uint32_t sig = tid; sig < (NSIG); sig += BLOCK) {   /* lane = signature */ \
+        const uint32_t reach = valid ? sig_reach_flat(s_flat, (NSIG), sig, s_cover, W) : 0u; \
+        s_r0[sig] = (uint16_t)entry_r(reach, W, 0); \
+        s_r1[sig] = (uint16_t)entry_r(reach, W, 1); \
+    } \
+    __syncthreads();
 template <int BLOCK, class TAIL>
 __device__ __forceinline__ void find1_launch(const Find1Args& a, const TAIL& tail) {
     extern __shared__ __align__(16) uint8_t lds_all[];
     uint8_t* lds = lds_all;
-    nhdfit_req* s_req = carve<nhdfit_req>(lds, 1);
-    PodSums* s_sum = carve<PodSums>(lds, 1);
-    PodHeader* s_hdr = carve<PodHeader>(lds, 1);
-    uint16_t* s_cover = carve<uint16_t>(lds, NHDFIT_MAX_CLASSES * (kMaxG + 1));
-    uint16_t* s_a0 = carve<uint16_t>(lds, kLoneGpuDim);
-    uint16_t* s_a1 = carve<uint16_t>(lds, kLoneGpuDim);
-    uint16_t* s_w0 = carve<uint16_t>(lds, 2 * kLoneCoreDim * 2);
-    uint16_t* s_w1 = carve<uint16_t>(lds, 2 * kLoneCoreDim * 2);
-    uint16_t* s_flat = carve<uint16_t>(lds, kDictLdsWords);
-    uint16_t* s_r0 = carve<uint16_t>(lds, kLoneMaxSigs);
-    uint16_t* s_r1 = carve<uint16_t>(lds, kLoneMaxSigs);
-    unsigned long long* s_best = carve<unsigned long long>(lds, 8);
+    NHDFIT_LONE_LDS(lds)
     uint8_t* lds_map = lds;                                              // the mapping tail's staging area
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
     const unsigned long long t0 = a.role_clock ? (unsigned long long)wall_clock64() : 0ull;
 
     // ---- the pod's masks
-    if (tid < sizeof(nhdfit_req) / 16) reinterpret_cast<uint4*>(s_req)[tid] = reinterpret_cast<const uint4*>(a.m.reqs)[tid];
-    for (uint32_t w = tid; w < a.d.flat_words / 2; w += BLOCK)          // (the stream is padded to an even word count)
-        reinterpret_cast<uint32_t*>(s_flat)[w] = reinterpret_cast<const uint32_t*>(a.d.flat)[w];
-    __syncthreads();
-    const nhdfit_req& r = *s_req;
-    const bool valid = req_valid(r);
-    if (tid == 0) {
-        *s_hdr = pod_header(r);
-        s_sum->G = r.n_groups; s_sum->W = 1u << (r.n_groups & 7u); s_sum->full = s_sum->W - 1;
-        s_sum->misc_smt = r.misc_smt; s_sum->misc_nosmt = r.misc_nosmt;
-    }
-    if (valid && tid < (1u << r.n_groups)) {                             // subset sums (pod_sums), one subset per thread
-        uint32_t g = 0, x = 0, y = 0;
-        for (uint32_t i = 0; i < r.n_groups; ++i)
-            if (tid >> i & 1) { g += r.gpus[i]; x += r.cpu_smt[i]; y += r.cpu_nosmt[i]; }
-        s_sum->gpu[tid] = g; s_sum->cpu_smt[tid] = x; s_sum->cpu_nosmt[tid] = y;
-    }
-    __syncthreads();
-    const uint32_t W = s_sum->W, G = s_sum->G;
-    if (valid && tid < a.d.ncls) class_cover(r, a.d.caps[tid], W, G, &s_cover[tid * (kMaxG + 1)]);
-    for (uint32_t k = tid; k < 2 * a.fg_dim; k += BLOCK) {
-        const uint32_t u = k >= a.fg_dim, f = u ? k - a.fg_dim : k;
-        (u ? s_a1 : s_a0)[f] = valid ? (uint16_t)entry_a(*s_sum, u, f) : (uint16_t)0;
-    }
-    for (uint32_t k = tid; k < 2 * (2 * a.fc_dim * 2); k += BLOCK) {     // [u][smt * fc_dim + c][m]
-        const uint32_t u = k >= 2 * a.fc_dim * 2, e = u ? k - 2 * a.fc_dim * 2 : k, m = e & 1, rec = e >> 1, smt = rec >= a.fc_dim, c = smt ? rec - a.fc_dim : rec;
-        (u ? s_w1 : s_w0)[e] = valid ? (uint16_t)entry_w(*s_sum, u, smt != 0, c, m) : (uint16_t)0;
-    }
-    __syncthreads();
-    for (uint32_t sig = tid; sig < a.nsig; sig += BLOCK) {               // lane = signature
-        const uint32_t reach = valid ? sig_reach_flat(s_flat, a.nsig, sig, s_cover, W) : 0u;
-        s_r0[sig] = (uint16_t)entry_r(reach, W, 0);
-        s_r1[sig] = (uint16_t)entry_r(reach, W, 1);
-    }
-    __syncthreads();
+    NHDFIT_LONE_POD_MASKS(BLOCK, tid, a.m.reqs, a.d, a.nsig, a.fc_dim, a.fg_dim)
     const LoneMasks t{s_a0, s_a1, s_w0, s_w1, s_r0, s_r1};
     const PodHeader h = *s_hdr;
     stamp(a.role_clock, 3, t0);

@@ -306,6 +306,22 @@ class Engine:
             self._chk(fn(self.ctx, _p(reqs), P, float(now), _p(cand), _p(counts), _p(stages)))
         return counts, stages
 
+    # ---- headroom: how many more replicas of each template every node can take (nhdfit_headroom) ------------------------------
+    def headroom(self, reqs: np.ndarray, cand: Optional[np.ndarray] = None, max_per_node: int = 512, per_node: bool = False):
+        """(sums [P] pack.HEADROOM_SUM, entries [P][n] uint16 or None) for ordinary requests (pack.REQ): per node the replicas that
+        fit back to back (pack.HEADROOM_COUNT_MASK) and the STOPPED / NOT_EVALUATED bits.  Nodes outside `cand` have 0; nothing of
+        the mirror changes."""
+        reqs = np.ascontiguousarray(reqs, dtype=pack.REQ)
+        P = len(reqs)
+        sums = np.zeros(P, pack.HEADROOM_SUM)
+        counts = np.zeros((P, self.n), np.uint16) if per_node else None
+        if cand is not None:
+            cand = np.ascontiguousarray(cand, dtype=np.uint64)
+            assert cand.shape == ((self.n + 63) // 64,)
+        if P:
+            self._chk(self.lib.nhdfit_headroom(self.ctx, _p(reqs), P, _p(cand), int(max_per_node), _p(sums), _p(counts)))
+        return sums, counts
+
     def big_commit(self, node: int, req: np.ndarray, mapping: np.ndarray, busy_time: float) -> np.ndarray:
         """The commit step of a big request on node `node` (ordinary or wide): updates the mirror, returns pack.BIG_PLACEMENT."""
         out = np.zeros((), pack.BIG_PLACEMENT)
@@ -708,6 +724,45 @@ class GroupEngine:
                 if st is not None:
                     stages[:, lo:hi] = st
         return counts, stages
+
+    def headroom(self, reqs: np.ndarray, cand: Optional[np.ndarray] = None, max_per_node: int = 512, per_node: bool = False):
+        """Engine.headroom over every shard: the sums added over the devices (nhdfit_group_headroom), the entries put together in
+        global node order."""
+        reqs = np.ascontiguousarray(reqs, dtype=pack.REQ)
+        P = len(reqs)
+        sums = np.zeros(P, pack.HEADROOM_SUM)
+        counts = np.zeros((P, self.n), np.uint16) if per_node else None
+        if cand is not None:
+            cand = np.ascontiguousarray(cand, dtype=np.uint64)
+        masks = [None if cand is None else np.ascontiguousarray(cand[lo // 64:(hi + 63) // 64]) for lo, hi in self._bounds]
+        if not P:
+            return sums, counts
+        if self.group is not None:
+            parts = [np.zeros((P, hi - lo), np.uint16) if per_node and hi > lo else None for lo, hi in self._bounds]
+            cptr = (ctypes.c_void_p * len(self.shards))(*[None if m is None else m.ctypes.data for m in masks])
+            sptr = (ctypes.c_void_p * len(self.shards))(*[None if x is None else x.ctypes.data for x in parts])
+            rc = self.lib.nhdfit_group_headroom(self.group, _p(reqs), P, cptr if cand is not None else None, int(max_per_node), _p(sums),
+                                                sptr if per_node else None)
+            if rc != 0:
+                raise _lib.NhdFitError(rc, (self.lib.nhdfit_group_last_error(self.group) or b"?").decode())
+        else:
+            parts = []
+            for k, s in enumerate(self.shards):
+                lo, hi = self._bounds[k]
+                if hi > lo:
+                    sm, ct = s.headroom(reqs, cand=masks[k], max_per_node=max_per_node, per_node=per_node)
+                    for f in ("replicas", "nodes_with_room", "saturated", "stopped", "not_evaluated"):
+                        sums[f] += sm[f]
+                    sums["max_on_one_node"] = np.maximum(sums["max_on_one_node"], sm["max_on_one_node"])
+                    sums["form"] = np.maximum(sums["form"], sm["form"])
+                    parts.append(ct)
+                else:
+                    parts.append(None)
+        if per_node:
+            for (lo, hi), ct in zip(self._bounds, parts):
+                if ct is not None:
+                    counts[:, lo:hi] = ct
+        return sums, counts
 
     def big_commit(self, node: int, req, mapping, busy_time):
         k = self._shard_of(node)

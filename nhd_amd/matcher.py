@@ -155,6 +155,54 @@ class Explanation:
         return f"Explanation({self.summary()!r})"
 
 
+def _spaced(v: int) -> str:
+    return f"{int(v):,}".replace(",", " ")
+
+
+class Headroom:
+    """How many more replicas of one pod template the nodes of `nl` can take (HipMatcher.Headroom): `replicas` (the sum - what the
+    scheduler's first-fit loop would place once busy windows have passed), `nodes_with_room`, `max_on_one_node`, `saturated` (nodes
+    that reached `max_per_node`), `stopped` (nodes whose run ended at a commit the reference raises on: their count is what
+    succeeded before it), `not_evaluated` (wide nodes, ENABLE_SHARING mirrors: no figure), `unmirrored` (nodes of `nl` the device
+    does not hold: they never match) and, when asked for, `per_node` (uint16 counts in `nl` order) with `flags` (the STOPPED /
+    NOT_EVALUATED bits of include/nhdfit.h beside them).  `form`: which kernel instantiation answered (pack.HEADROOM_FORM_*).
+    `error`: why the template itself could not be evaluated - then nothing is a number: every node counts as not evaluated."""
+
+    def __init__(self, nodes: int, names: Optional[List[str]] = None, replicas: int = 0, nodes_with_room: int = 0, max_on_one_node: int = 0,
+                 saturated: int = 0, stopped: int = 0, not_evaluated: int = 0, unmirrored: int = 0, form: int = 0, max_per_node: int = 0,
+                 per_node: Optional[np.ndarray] = None, flags: Optional[np.ndarray] = None, error: Optional[str] = None):
+        self.nodes, self._names = nodes, names
+        self.replicas, self.nodes_with_room, self.max_on_one_node = int(replicas), int(nodes_with_room), int(max_on_one_node)
+        self.saturated, self.stopped, self.not_evaluated, self.unmirrored = int(saturated), int(stopped), int(not_evaluated), int(unmirrored)
+        self.form, self.max_per_node = int(form), int(max_per_node)
+        self.per_node, self.flags, self.error = per_node, flags, error
+
+    def by_node(self) -> Dict[str, int]:
+        """name -> replicas (per_node=True calls only)."""
+        if self.per_node is None:
+            raise ValueError("by_node() needs the per-node counts: ask for per_node=True" if self.error is None else f"not evaluated: {self.error}")
+        return {nm: int(k) for nm, k in zip(self._names, self.per_node)}
+
+    def summary(self) -> str:
+        """"1 234 more replicas on 410 of 65 536 nodes (most on one node: 7)", and what qualifies it."""
+        if self.error is not None:
+            return f"the pod was not evaluated against the {_spaced(self.nodes)} nodes: {self.error}."
+        text = f"{_spaced(self.replicas)} more replicas on {_spaced(self.nodes_with_room)} of {_spaced(self.nodes)} nodes (most on one node: {_spaced(self.max_on_one_node)})"
+        notes = []
+        if self.saturated:
+            notes.append(f"{_spaced(self.saturated)} reached the limit of {_spaced(self.max_per_node)} per node")
+        if self.stopped:
+            notes.append(f"{_spaced(self.stopped)} stopped at a placement the scheduler would fail on")
+        if self.not_evaluated:
+            notes.append(f"{_spaced(self.not_evaluated)} not evaluated")
+        if self.unmirrored:
+            notes.append(f"{_spaced(self.unmirrored)} not mirrored on the device")
+        return text + ("; " + ", ".join(notes) if notes else "")
+
+    def __repr__(self) -> str:
+        return f"Headroom({self.summary()!r})"
+
+
 def check_interpreter_set_model() -> None:
     import itertools
     for k, want in _SET_ORDER_PROBES.items():
@@ -770,6 +818,78 @@ class HipMatcher:
                 continue
             out.append(Explanation({s: int(counts[p, k]) for k, s in enumerate(STAGES)}, n_unmirrored,
                                    stages[p, order] if per_node else None, nodes=len(nl)))
+        return out
+
+    def Headroom(self, nl: Dict[str, object], top, pod_groups: Optional[Sequence[str]] = None, per_node: bool = False,
+                 max_per_node: int = 512, strict: Optional[bool] = None) -> Headroom:
+        """HeadroomMany for one pod template."""
+        return self.HeadroomMany(nl, [top], None if pod_groups is None else [pod_groups], per_node=per_node, max_per_node=max_per_node,
+                                 strict=strict)[0]
+
+    def HeadroomMany(self, nl: Dict[str, object], tops: Sequence[object], pod_groups: Optional[Sequence[Sequence[str]]] = None,
+                     per_node: bool = False, max_per_node: int = 512, strict: Optional[bool] = None) -> List[Headroom]:
+        """How many more replicas of each pod template of `tops` the nodes of `nl` can take, counted on the device (nhdfit_headroom):
+        per node the number of times FindNode -> SetPhysicalIdsFromMapping -> ClaimPodNICResources succeeds back to back on a private
+        copy of the node, busy windows out of the way (capacity, not rate: there is no `now`).  The mirror state is the one
+        FindNodes(nl, tops, pod_groups) answers from (pending changes are flushed the same way); nothing about it changes.
+        `max_per_node` (1..16383) bounds a node's run - a template that asks for nothing would fit for ever.  Wide nodes and
+        ENABLE_SHARING mirrors are reported as not evaluated, never as a number.  A template no request record can express (5..8
+        processing groups, hugepages beyond the pod tile, an unsupported request) or a device error comes back with `error` set
+        and everything not evaluated - `strict=True` (default: the matcher's) raises instead."""
+        strict = self.strict if strict is None else strict
+        n_pods = len(tops)
+        if n_pods == 0:
+            return []
+        if not 1 <= int(max_per_node) <= pack.HEADROOM_COUNT_MASK:
+            raise ValueError(f"max_per_node is {max_per_node} (1 .. {pack.HEADROOM_COUNT_MASK})")
+        names = list(nl)
+        if len(nl) == 0:
+            return [Headroom(0, names, max_per_node=max_per_node, per_node=np.zeros(0, np.uint16) if per_node else None,
+                             flags=np.zeros(0, np.uint16) if per_node else None) for _ in range(n_pods)]
+        errors: Dict[int, str] = {}
+        for p, top in enumerate(tops):
+            if len(top.proc_groups) == 0:
+                errors[p] = "it has no processing groups (the reference fails on such a pod, Matcher.py:346)"
+            elif pack.needs_general_path(top):
+                errors[p] = "it takes the general path (5..8 processing groups or a hugepage request beyond the pod tile), which headroom does not cover"
+        if errors and strict:
+            raise pack.UnsupportedNode(f"headroom: pod {min(errors)} of the call: {errors[min(errors)]}")
+        cand = self._sync_mirror(nl)
+        n_unmirrored = sum(1 for nm in nl if nm in self.packer.unmirrored)
+        idx = [p for p in range(n_pods) if p not in errors]
+        sums, counts = None, None
+        if idx:
+            beyond: List[Tuple[int, str]] = []
+            reqs = self.packer.digest_many([tops[p] for p in idx], None if pod_groups is None else [pod_groups[p] for p in idx], unsupported=beyond)
+            for k, why in beyond:
+                if strict:
+                    raise pack.UnsupportedNode(f"headroom: pod {idx[k]} of the call: {why}")
+                errors[idx[k]] = f"it cannot be expressed as a request record ({why})"
+            try:
+                self.packer.close_signatures()             # every NIC state a commit can produce has a signature
+                self.engine.set_dictionary(self.packer)
+                sums, counts = self.engine.headroom(reqs, cand=cand, max_per_node=int(max_per_node), per_node=per_node)
+            except NhdFitError as e:
+                if strict:
+                    raise
+                for p in idx:
+                    errors.setdefault(p, f"the device could not evaluate it ({e})")
+        for p in sorted(errors):
+            self.logger.error("headroom: pod %d of the call is not evaluated: %s", p, errors[p])
+        order = np.fromiter((self._index[nm] for nm in nl), dtype=np.int64, count=len(nl)) if per_node else None
+        out = []
+        for p in range(n_pods):
+            if p in errors:
+                out.append(Headroom(len(nl), names, not_evaluated=len(nl), unmirrored=n_unmirrored, max_per_node=max_per_node, error=errors[p]))
+                continue
+            k = idx.index(p)
+            sm = sums[k]
+            e = counts[k][order] if per_node else None
+            out.append(Headroom(len(nl), names, replicas=sm["replicas"], nodes_with_room=sm["nodes_with_room"], max_on_one_node=sm["max_on_one_node"],
+                                saturated=sm["saturated"], stopped=sm["stopped"], not_evaluated=sm["not_evaluated"], unmirrored=n_unmirrored,
+                                form=sm["form"], max_per_node=max_per_node,
+                                per_node=None if e is None else (e & np.uint16(pack.HEADROOM_COUNT_MASK)),
+                                flags=None if e is None else (e & np.uint16(pack.HEADROOM_STOPPED | pack.HEADROOM_NOT_EVALUATED))))
         return out
 
     @property

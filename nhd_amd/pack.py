@@ -91,6 +91,11 @@ PLACEMENT = np.dtype([("proc_take", "<u8", (4,)), ("proc_pair", "<u8", (4,)), ("
                       ("misc_take", "<u8"), ("misc_pair", "<u8"), ("gpu", "u1", (4, 8)), ("numa", "i1", (5,)), ("status", "u1"),
                       ("pad", "u1", (2,)), ("proc_late", "<u8", (4,)), ("help_late", "<u8", (4,)), ("misc_late", "<u8")])
 COMMIT_OK, COMMIT_WOULD_RAISE, COMMIT_NEW_SIG, COMMIT_WIDE = 0, 1, 2, 3
+# nhdfit_headroom_sum and the bits of a per-node headroom entry (include/nhdfit.h NHDFIT_HEADROOM_*)
+HEADROOM_SUM = np.dtype([("replicas", "<u8"), ("nodes_with_room", "<u4"), ("max_on_one_node", "<u4"), ("saturated", "<u4"), ("stopped", "<u4"),
+                         ("not_evaluated", "<u4"), ("form", "<u4")])
+HEADROOM_COUNT_MASK, HEADROOM_STOPPED, HEADROOM_NOT_EVALUATED = 0x3FFF, 0x4000, 0x8000
+HEADROOM_FORM_WAVE, HEADROOM_FORM_GENERIC = 1, 2
 # nodes beyond the fast layout: one self-contained record each (include/nhdfit.h nhdfit_wide_node)
 WIDE_MAX_NUMA, WIDE_CORE_WORDS, WIDE_MAX_CORES_PER_NUMA = 4, 8, 128
 WIDE = np.dtype([("t0", "<u8", (WIDE_CORE_WORDS,)), ("t1", "<u8", (WIDE_CORE_WORDS,)), ("o0", "<u8", (WIDE_CORE_WORDS,)), ("o1", "<u8", (WIDE_CORE_WORDS,)),

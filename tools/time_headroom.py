@@ -1,0 +1,74 @@
+#!/usr/bin/env python3
+"""Cost of nhdfit_headroom through ctypes (median / min ms of repeated calls behind a warm-up; one JSON line):
+
+  * one GPU-less template of BASELINE config 2 (4 096 nodes) and one template of config 4 (65 536 nodes), whole cluster, sums only and
+    with the per-node entries;
+  * against the only route to the same total without the call: nhdfit_schedule_batch(apply=0) over replicas + 1 copies of the
+    template, same mirror (`--route-only=R2,R4`: that leg alone, given the two totals - a copy of this file in a checkout of the parent
+    commit, which has no nhdfit_headroom, gives the same-box comparison);
+  * one template on a cluster with no room at all (every node in maintenance) against nhdfit_find for the same pod.
+
+`python tools/time_headroom.py` on the GPU box; kernel time from a separate
+`rocprofv3 --kernel-trace --stats -- python tools/time_headroom.py --kernels` run (headroom calls only)."""
+import json, os, sys, time
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+from nhd_amd import pack
+from nhd_amd.engine import Engine
+from workload import planes, refmodel, synth
+
+ROUTE = [a for a in sys.argv[1:] if a.startswith("--route-only=")]       # --route-only=<replicas c2>,<replicas c4>: the totals a full run printed
+ROUTE_ONLY, KERNELS = bool(ROUTE), "--kernels" in sys.argv
+TOTALS = dict(zip(("c2", "c4"), (int(x) for x in ROUTE[0].split("=")[1].split(",")))) if ROUTE else {}
+
+
+def timed(fn, reps):
+    fn(); fn()
+    xs = []
+    for _ in range(reps):
+        t0 = time.perf_counter(); fn(); xs.append((time.perf_counter() - t0) * 1e3)
+    return {"ms_median": float(np.median(xs)), "ms_min": float(min(xs))}
+
+
+def shape(cfg, n, want_gpu, full=False):
+    spec = synth.make_cluster(cfg, n_nodes=n)
+    if full:
+        spec.maintenance[:] = True
+    pods, _ = synth.make_pods(cfg, n_pods=64)
+    s = next(s for s in pods if any(g["gpus"] for g in s["groups"]) == want_gpu and len(s["groups"]) == 2)
+    pk = pack.Packer()
+    table = planes.planes_from_spec(pk, spec)
+    req = pk.digest_many([refmodel.make_topology(s)])
+    pk.close_signatures()
+    eng = Engine(0)
+    eng.set_dictionary(pk)
+    eng.upload(table)
+    return spec, pk, req, eng
+
+
+out = {}
+for key, cfg, n in (("c2", 2, 4096), ("c4", 4, 65536)):
+    spec, pk, req, eng = shape(cfg, n, want_gpu=False)
+    r = {"nodes": n}
+    if not ROUTE_ONLY:
+        sums, _ = eng.headroom(req)
+        r.update(replicas=int(sums["replicas"][0]), nodes_with_room=int(sums["nodes_with_room"][0]), max_on_one_node=int(sums["max_on_one_node"][0]),
+                 form=int(sums["form"][0]))
+        r["headroom_sums"] = timed(lambda: eng.headroom(req), 30)
+        r["headroom_per_node"] = timed(lambda: eng.headroom(req, per_node=True), 30)
+    if not KERNELS:
+        total = r["replicas"] if "replicas" in r else TOTALS[key]
+        copies = np.repeat(req, total + 1)
+        node = eng.schedule_batch(copies, spec.clock_now, pk, apply=False)[0]
+        r["route_placed"] = int((node >= 0).sum())
+        r["route_schedule_batch"] = timed(lambda: eng.schedule_batch(copies, spec.clock_now, pk, apply=False), 5)
+    out[key] = r
+    eng.close()
+if not ROUTE_ONLY:
+    spec, pk, req, eng = shape(4, 65536, want_gpu=False, full=True)
+    sums, _ = eng.headroom(req)
+    out["c4_no_room"] = {"nodes": 65536, "replicas": int(sums["replicas"][0]), "headroom_sums": timed(lambda: eng.headroom(req), 50)}
+    if not KERNELS:
+        out["c4_no_room"]["find_one"] = timed(lambda: eng.find(req, spec.clock_now, want_bitmap=False, want_map=True), 50)
+    eng.close()
+print(json.dumps(out))
