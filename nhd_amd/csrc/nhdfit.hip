@@ -167,20 +167,13 @@ struct nhdfit_ctx {
     Pipe pipe[kPipes];
     StreamLedger streams;                // stream k = pipe k's, kRed = the reduce stream's; use(k) hands out a handle and marks the stream
     double enq_us = 0, enq_launch_us = 0, enq_events_us = 0; uint64_t enq_n = 0;   // tuning aid (NHDFIT_ENQ_PROF): host time of nhdfit_enqueue_step, of the launch calls, of the event records
-    bool dual = tune_env("NHDFIT_ONE_PIPE") == nullptr;   // tuning aid: NHDFIT_ONE_PIPE=1 keeps every step on pipe 0
-    uint64_t n_enq = 0;                  // steps enqueued since the last stage_requests (step k runs on pipe k % 2)
+    uint64_t n_enq = 0;                  // steps enqueued since the last stage_requests (step k runs on pipe k % npipes)
     int last_pipe = 0;                   // the pipe of the most recent step (nhdfit_fetch reads its results)
     uint64_t staged_gen = 1;             // bumped whenever pipe 0's stream gets staging work (requests, work items, node records): the other pipes wait for it once
-    int npipes = 2;                      // pipes the staged batch's steps are dealt to: 2, or 3 (nhdfit_enqueue_step decides per batch)
+    int npipes = 2;                      // pipes the staged batch's steps are dealt to: 2, or 3 (nhdfit_enqueue_step decides per batch; NHDFIT_PIPES)
     bool geom_big = true;                // 512-thread step blocks (256 for small problems)
-    uint32_t digest_parts = tune_env("NHDFIT_DIGEST_PARTS") ? (uint32_t)atoi(tune_env("NHDFIT_DIGEST_PARTS")) : 2;   // tuning aid
-    uint32_t side_prio = tune_env("NHDFIT_SIDE_PRIO") ? (uint32_t)atoi(tune_env("NHDFIT_SIDE_PRIO")) : 1;   // tuning aid
-    int seq_pods = tune_env("NHDFIT_SEQ_PODS") && atoi(tune_env("NHDFIT_SEQ_PODS")) == 8 ? 8 : 16;   // tuning aid: pods per round of the sequential kernel
-    uint32_t choose_split = tune_env("NHDFIT_CHOOSE_SPLIT") ? (uint32_t)atoi(tune_env("NHDFIT_CHOOSE_SPLIT")) : 16;   // tuning aid: wavefronts per tile
-    bool split = tune_env("NHDFIT_SPLIT") != nullptr;
-    bool role_kernels = tune_env("NHDFIT_ROLE_KERNELS") != nullptr;   // profiling aid: every role as a kernel of its own (512-thread geometry only)
-    DevBuf<unsigned long long> role_clock;            // profiling aid: NHDFIT_ROLE_TIMES=<step> prints the role windows of that step
-    int64_t role_step = tune_env("NHDFIT_ROLE_TIMES") ? atoll(tune_env("NHDFIT_ROLE_TIMES")) : -1;   // profiling aid: launch the side roles apart from the fit role
+    DevBuf<unsigned long long> role_clock;            // profiling aid: NHDFIT_ROLE_TIMES=<step> prints the role windows of that step's launch,
+    int64_t role_step = tune_env("NHDFIT_ROLE_TIMES") ? atoll(tune_env("NHDFIT_ROLE_TIMES")) : -1;   // and of every single-launch find
     std::string err;
     hipDeviceProp_t prop;
 
@@ -213,7 +206,6 @@ struct nhdfit_ctx {
     uint32_t pair_D[2] = {0, 0};
     uint32_t crow_D[2] = {0, 0};          // pair-table dimensions the records' C rows (NodeRec::flags) are written for; crow_stale: a staged
     bool crow_stale = false;              // batch of more than a tile asks for others - k_xcrow rewrites them in front of its first step
-    bool pair_rows = !(tune_env("NHDFIT_PAIR") && atoi(tune_env("NHDFIT_PAIR")) == 0);   // tuning aid: NHDFIT_PAIR=0 keeps the six-fetch sweep
 
     // requests / results
     DevBuf<nhdfit_req> reqs; uint32_t P = 0;
@@ -234,7 +226,6 @@ struct nhdfit_ctx {
     DevBuf<double> rec_bt[kWClasses];    // busy times beside the records, in the records' (lane) order
     // lane order of the chunks' records (step_kernel.h k_xorder): built for the pair-table dimensions order_D; ord_all = every chunk is
     // (re)dealt at the next step (a staged batch changed a dimension); chunks k_xrecords rewrites are dealt right behind it
-    bool lane_order = !(tune_env("NHDFIT_LANE_ORDER") && atoi(tune_env("NHDFIT_LANE_ORDER")) == 0);   // tuning aid: NHDFIT_LANE_ORDER=0 keeps node order
     uint32_t order_D[2] = {~0u, ~0u}; bool ord_all = false;
     DevBuf<unsigned long long> xkeys; DevBuf<uint32_t> xids; DevBuf<uint64_t> xcls; DevBuf<uint32_t> xnx;
     uint32_t rec_lo = 0, rec_hi = 0; bool rec_all = true;
@@ -242,14 +233,9 @@ struct nhdfit_ctx {
     // signatures some interned class refers to, ascending (DigestArgs::sig_list): rebuilt when classes are added; all_sigs: the
     // digest of the step being enqueued forms every signature's rows (mode B's snapshot pass reads them for committed nodes)
     DevBuf<uint16_t> sig_use; uint32_t n_sig_use = 0, sig_use_nx = 0; bool all_sigs = false;
-    bool sig_use_on = tune_env("NHDFIT_ALL_SIGS") == nullptr;   // tuning aid: NHDFIT_ALL_SIGS=1 digests every signature in every step
-    uint32_t fit_blocks = tune_env("NHDFIT_FIT_BLOCKS") ? (uint32_t)atoi(tune_env("NHDFIT_FIT_BLOCKS")) : 0;   // tuning aid: blocks of the fit role
-    bool use_choose_tab = tune_env("NHDFIT_NO_CHOOSE_TABLE") == nullptr;   // tuning aid: run the set model for every shape
     // set-layout state machine for three-group pods (set_states.h): verified against the model on the host
-    // (tests/test_pyset_emulation.py), parity-green and 10 % faster per step on the GPU (profiles/r02):
-    // on by default, NHDFIT_NO_SET_STATES=1 runs the insertion-by-insertion model instead
+    // (tests/test_pyset_emulation.py), parity-green and 10 % faster per step on the GPU than the insertion-by-insertion model (profiles/r02)
     DevBuf<uint64_t> st_info; DevBuf<uint32_t> st_next, st_asc; uint32_t st_n = 0;
-    bool use_set_states = tune_env("NHDFIT_NO_SET_STATES") == nullptr;
     // mode B
     DevBuf<uint64_t> nogpu, taken, tile_masks; DevBuf<int32_t> touched; DevBuf<uint16_t> gl_tiles; std::vector<SeqResult> seq_host; DevBuf<UndoRec> undo; DevBuf<SeqResult> seq_out; DevBuf<nhdfit_placement> seq_place;
     DevBuf<uint32_t> order, seq_counters;
@@ -403,6 +389,77 @@ int sync_all(nhdfit_ctx* c) {
     return NHDFIT_OK;
 }
 
+// Nodes [lo, hi) changed in the mirror (upload, commit, delta): their records are stale until ensure_records rewrites them.
+void mark_records_stale(nhdfit_ctx* c, uint32_t lo, uint32_t hi) {
+    if (c->rec_lo == c->rec_hi) { c->rec_lo = lo; c->rec_hi = hi; }
+    else { c->rec_lo = std::min(c->rec_lo, lo); c->rec_hi = std::max(c->rec_hi, hi); }
+}
+
+// No step of a staged batch is in flight any more: every pipe's phase counters, and the counters of the batch's steps, start over.
+void reset_step_counters(nhdfit_ctx* c) {
+    for (Pipe& p : c->pipe) p.n_dig = p.n_fit = p.n_shaped = p.n_chosen = p.n_finished = 0;
+    c->n_enq = 0;
+    c->last_pipe = 0;
+}
+
+// The sequence number the next single-launch call stores behind its results (never 0, never kFindAborted).
+uint32_t next_find_seq(nhdfit_ctx* c) {
+    uint32_t seq = ++c->find_seq;
+    if (seq == 0u || seq == kFindAborted) seq = c->find_seq = 1u;
+    return seq;
+}
+
+// What every form of a find leaves in the statistics.
+void store_find_stats(nhdfit_ctx* c, uint64_t evals, uint64_t bytes) {
+    c->stats.evals_last = evals;
+    c->stats.bytes_last = bytes;
+    c->stats.nodes = c->n; c->stats.nsig = c->nsig; c->stats.ncls = c->ncls; c->stats.lds_bytes = c->lds_bytes;
+}
+
+// Tuning aid (NHDFIT_FIND_PROF): host time between the phases of a call, one line per phase on stderr.
+struct PhaseTimer {
+    const char* call; uint32_t P;
+    std::chrono::steady_clock::time_point t_prev = std::chrono::steady_clock::now();
+    static bool on() { static const bool prof = tune_env("NHDFIT_FIND_PROF") != nullptr; return prof; }
+    void lap(const char* what) {
+        if (!on()) return;
+        const auto t1 = std::chrono::steady_clock::now();
+        fprintf(stderr, "[nhdfit] %s P=%u %s %.1f us\n", call, P, what, std::chrono::duration<double, std::micro>(t1 - t_prev).count());
+        t_prev = t1;
+    }
+};
+
+// Tuning aid (NHDFIT_ROLE_TIMES): the launch's roles stamp their first start / last end into role_clock[2 * slot], [2 * slot + 1]
+// (100 MHz ticks).  arm_role_clock readies `slots` pairs behind stream k (the words behind them, up to kClockWords, are zero: the step's
+// fit role counts its per-block phases there, FitArgs::clk); report_role_clock waits for stream k and prints one `line` - (name, start,
+// end), in us after the earliest start - per slot that ran.
+constexpr int kClockWords = 32;
+const char* const kRoleNames[] = {"choose", "shapes", "finish", "digest", "fit", "commit"};
+int arm_role_clock(nhdfit_ctx* c, int k, int slots) {
+    HIPCHK(c, c->role_clock.reserve(kClockWords));
+    unsigned long long init[kClockWords] = {0};
+    for (int s = 0; s < slots; ++s) init[2 * s] = ~0ull;
+    HIPCHK(c, hipMemcpyAsync(c->role_clock.p, init, sizeof init, hipMemcpyHostToDevice, c->streams.use(k)));
+    HIPCHK(c, c->streams.wait(k));
+    return NHDFIT_OK;
+}
+int report_role_clock(nhdfit_ctx* c, int k, int slots, const char* line) {
+    unsigned long long t[kClockWords];
+    HIPCHK(c, c->streams.wait(k));
+    HIPCHK(c, hipMemcpy(t, c->role_clock.p, sizeof t, hipMemcpyDeviceToHost));
+    if (t[24]) {                                                // (the step's fit blocks: t[16..23] summed / latest, t[24] how many)
+        const double nb = (double)t[24];
+        fprintf(stderr, "[nhdfit] step %lld fit blocks (%llu): mean / latest after the block's start - staged %.2f / %.2f, pair table %.2f / %.2f, sweep done %.2f / %.2f, "
+                        "scores out %.2f / %.2f us\n", (long long)c->role_step, t[24], t[16] * 0.01 / nb, t[17] * 0.01, t[18] * 0.01 / nb, t[19] * 0.01,
+                t[20] * 0.01 / nb, t[21] * 0.01, t[22] * 0.01 / nb, t[23] * 0.01);
+    }
+    unsigned long long first = ~0ull;
+    for (int s = 0; s < slots; ++s) first = t[2 * s] < first ? t[2 * s] : first;
+    for (int s = 0; s < slots; ++s)
+        if (t[2 * s + 1]) fprintf(stderr, line, kRoleNames[s], (t[2 * s] - first) * 0.01, (t[2 * s + 1] - first) * 0.01);
+    return NHDFIT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -471,7 +528,7 @@ int nhdfit_create(int device_id, nhdfit_ctx** out) {
     if (e == hipSuccess) {
         hipLaunchKernelGGL(k_build_asc, dim3((kAscEntries + 255) / 256), dim3(256), 0, c->streams.use(0), c->asc.p);
         e = hipGetLastError();
-        if (e == hipSuccess && c->use_set_states) {
+        if (e == hipSuccess) {
             std::vector<uint64_t> info;
             std::vector<uint32_t> next, asc;
             build_set_states(info, next, asc);
@@ -625,8 +682,7 @@ int nhdfit_set_dictionary(nhdfit_ctx* c, uint32_t max_cores_per_numa, uint32_t m
         static_assert(kPoolSlotsMax == kPoolSlots, "dict_stream.h and step_digest.h agree on the slot capacity");
         const SigDict hd{sig_off, pool_off, pool_glimit, cc, nsig};
         const std::vector<uint16_t> f2 = build_typed_stream(hd);
-        static const bool typed_off = tune_env("NHDFIT_NO_POOL_TYPES") != nullptr;   // tuning aid: the digest walks pool by pool
-        c->flat2_words = !typed_off ? (uint32_t)f2.size() : 0;
+        c->flat2_words = (uint32_t)f2.size();
         if (c->flat2_words) {
             HIPCHK(c, c->sig_flat2.reserve(f2.size()));
             HIPCHK(c, hipMemcpy(c->sig_flat2.p, f2.data(), f2.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
@@ -638,12 +694,6 @@ int nhdfit_set_dictionary(nhdfit_ctx* c, uint32_t max_cores_per_numa, uint32_t m
     c->max_cores = max_cores_per_numa;
     c->max_gpus = max_gpus_per_numa;
     c->P = 0;                                       // staged tables (if any) were built for the old dictionary
-#ifdef NHDFIT_TUNING
-    HIPCHK(c, hipFuncSetAttribute((const void*)k_fit_only<512>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HIPCHK(c, hipFuncSetAttribute((const void*)k_fit_only<256>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HIPCHK(c, hipFuncSetAttribute((const void*)k_role<512, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HIPCHK(c, hipFuncSetAttribute((const void*)k_role<512, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-#endif
     HIPCHK(c, hipFuncSetAttribute((const void*)k_step<512>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     HIPCHK(c, hipFuncSetAttribute((const void*)k_find<256>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     HIPCHK(c, hipFuncSetAttribute((const void*)k_find1<256>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
@@ -705,8 +755,7 @@ int nhdfit_upload_nodes(nhdfit_ctx* c, uint32_t first, uint32_t count, const nhd
     HIPCHK(c, hipSetDevice(c->dev));
     TRY(sync_all(c));     // a step in flight must not see a half-written record
     if (first + count > c->n) { c->rec_all = true; c->n_items = 0; }   // the node count changes: the last chunk's padding moves
-    else if (c->rec_lo == c->rec_hi) { c->rec_lo = first; c->rec_hi = first + count; }
-    else { c->rec_lo = std::min(c->rec_lo, first); c->rec_hi = std::max(c->rec_hi, first + count); }
+    else mark_records_stale(c, first, first + count);
     HIPCHK(c, hipMemcpy(c->p0.p + first, p0, count * sizeof *p0, hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(c->p1.p + first, p1, count * sizeof *p1, hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(c->p2.p + first, p2, count * sizeof *p2, hipMemcpyHostToDevice));
@@ -750,7 +799,7 @@ int refresh_layouts(nhdfit_ctx* c) {
     // while a block's LDS stays within a third of the CU's (three 512-thread blocks per CU is what the registers allow, and
     // the launch's dynamic LDS is one size for all of its blocks).
     c->pair_D[0] = c->pair_D[1] = 0;
-    if (c->pair_rows && !spill) {
+    if (!spill) {
 #ifndef NHDFIT_LDS_BLOCKS
 #define NHDFIT_LDS_BLOCKS 3
 #endif
@@ -830,14 +879,7 @@ namespace {
 int stage_requests(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, bool defer_small_copies, bool defer_request_copy, size_t tail_bytes) {
     if (!reqs || !P) return fail(c, NHDFIT_E_INVAL, "no requests");
     if (!c->nsig) return fail(c, NHDFIT_E_STATE, "set the dictionary first");
-    static const bool prof = tune_env("NHDFIT_FIND_PROF") != nullptr;      // tuning aid: host-side phase times of the staging
-    auto t_prev = std::chrono::steady_clock::now();
-    auto lap = [&](const char* what) {
-        if (!prof) return;
-        const auto t1 = std::chrono::steady_clock::now();
-        fprintf(stderr, "[nhdfit]   stage P=%u %s %.1f us\n", P, what, std::chrono::duration<double, std::micro>(t1 - t_prev).count());
-        t_prev = t1;
-    };
+    PhaseTimer prof{"  stage", P};
     // (no stream holds a mark - a single-launch find of a batch that saw its word left them so, and nothing was enqueued since: asking
     // the first stream would only make the runtime reap that launch now - ~12 us of every batch call)
     const bool idle = c->streams.all_clean() && c->ev_pending == 0;
@@ -847,10 +889,8 @@ int stage_requests(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, bool defer
         TRY(drain_events(c));
     } else
         TRY(check_skipped_waits(c, "stage_requests"));
-    lap("streams idle, events read");
-    for (Pipe& p : c->pipe) p.n_dig = p.n_fit = p.n_shaped = p.n_chosen = p.n_finished = 0;
-    c->n_enq = 0;
-    c->last_pipe = 0;
+    prof.lap("streams idle, events read");
+    reset_step_counters(c);
     c->staged_gen++;
     const uint32_t tiles = (P + kTile - 1) / kTile;
     // Pods are staged sorted by request class so that 64-pod tiles are homogeneous (narrow table rows, fast sweep of
@@ -866,7 +906,7 @@ int stage_requests(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, bool defer
     const size_t tail_records = (tail_bytes + sizeof(nhdfit_req) - 1) / sizeof(nhdfit_req);   // (room behind the records for what rides the same copy)
     HIPCHK(c, c->reqs.reserve((size_t)P + tail_records));
     for (Pipe& p : c->pipe)
-        if (tiles > p.dig_count.cap) {                 // (the digest role leaves its arrival counters at zero: cleared when the buffer is new)
+        if (tiles > p.dig_count.cap) {                 // (DigestArgs::count: nothing counts there while one block forms a tile's signature rows)
             HIPCHK(c, p.dig_count.reserve(std::max<size_t>(tiles, 256)));
             HIPCHK(c, hipMemsetAsync(p.dig_count.p, 0, p.dig_count.cap * sizeof(uint32_t), c->streams.use(0)));
         }
@@ -876,7 +916,7 @@ int stage_requests(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, bool defer
             HIPCHK(c, p.score[b].reserve(P));
             HIPCHK(c, p.maps[b].reserve(P));
         }
-    lap("order, buffers");
+    prof.lap("order, buffers");
     c->n_big_pods = seen.n_big;
     HIPCHK(c, c->pin_reqs.reserve((size_t)P + tail_records));
     nhdfit_req* sorted = c->pin_reqs.p;                                   // (free again: sync_all above waited for the last copy out of it)
@@ -899,7 +939,7 @@ int stage_requests(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, bool defer
             for (uint32_t i = lo; i < hi; ++i)
                 if (req_valid(sorted[i])) c->max_demand[w] = std::max(c->max_demand[w], req_max_demand(sorted[i]));
     }
-    lap("gather");
+    prof.lap("gather");
     // ONE copy: the batch in four pieces, each piece's transfer beside the next piece's gather, was measured and is slower - every copy
     // command costs the copy engine ~10 us before its first byte moves (config 4: 0.166 -> 0.193 ms per call, profiles/r05)
     c->reqs_deferred = defer_request_copy;
@@ -913,9 +953,9 @@ int stage_requests(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, bool defer
     c->hp_rows = (uint32_t)hp_max + 2;
     c->n_items = 0;                                 // the fit role's work items are rebuilt at the next step
     c->use_cand = false;
-    lap("copies enqueued");
+    prof.lap("copies enqueued");
     TRY(refresh_layouts(c));
-    lap("layouts");
+    prof.lap("layouts");
     // a node's C row depends on the pair table's dimension: a batch that changes it has the chunks' records dealt to the lanes again
     // (ensure_records, in front of the batch's first step) - a full tile and more only: smaller batches are latency, not throughput
     if (P > (uint32_t)kTile && (c->pair_D[0] != c->order_D[0] || c->pair_D[1] != c->order_D[1])) c->ord_all = true;
@@ -958,7 +998,7 @@ int order_chunks(nhdfit_ctx* c, uint32_t first_chunk, uint32_t n_chunks, bool ev
 int ensure_records(nhdfit_ctx* c) {
     const uint32_t all_chunks = (c->n + 63) / 64;
     // dealing the records to the lanes pays where the fit role is more than a launch: from 128 chunks on
-    const bool deal = c->lane_order && all_chunks >= 128;
+    const bool deal = all_chunks >= 128;
     // the C rows the records carry, for the staged batch's pair-table dimensions: every record's flags word (unless all records are
     // about to be written anyway) - in front of whatever else rewrites records, which then writes for the new dimensions too
     const bool crow = c->crow_stale;
@@ -1019,7 +1059,7 @@ int ensure_records(nhdfit_ctx* c) {
             for (Pipe& p : c->pipe)                             // them - it is digested again (nhdfit_enqueue_step looks here first)
                 if (p.n_dig > p.n_fit) p.n_dig = p.n_fit;
         c->nx = nx[0];
-        if (c->sig_use_on && c->sig_use_nx != c->nx) {              // the signatures the classes refer to (classes are only ever added)
+        if (c->sig_use_nx != c->nx) {              // the signatures the classes refer to (classes are only ever added)
             std::vector<uint64_t> keys(c->nx);
             if (c->nx) HIPCHK(c, hipMemcpy(keys.data(), c->xcls.p, (size_t)c->nx * sizeof(uint64_t), hipMemcpyDeviceToHost));
             std::vector<uint8_t> used(0x10000u, 0);
@@ -1054,13 +1094,13 @@ int ensure_records(nhdfit_ctx* c) {
 
 // Work items of the fit role (one block each): the tiles' chunk ranges cut so that every block carries about the
 // same cost - a chunk of a tile with W assignments costs ~(6 + W) - and the block count is a fixed multiple of what
-// the chip holds at once (NHDFIT_FIT_BLOCKS overrides the target).  Wide tiles first: longest-first keeps the tail
-// of the launch short.  Small problems simply get one wavefront-run per chunk.
+// the chip holds at once.  Wide tiles first: longest-first keeps the tail of the launch short.  Small problems simply
+// get one wavefront-run per chunk.
 int build_items(nhdfit_ctx* c, uint32_t nw, bool batch_find = false) {
     const uint32_t tiles = (c->P + kTile - 1) / kTile, chunks = (c->n + 63) / 64;
     const uint32_t cus = (uint32_t)c->prop.multiProcessorCount;
     // two of the three 512-thread blocks a CU holds (the side roles of the same launch live in the third slot)
-    uint32_t target = c->fit_blocks ? c->fit_blocks : cus * (nw == 8 ? 2u : 5u);          // see k_step: the fit role leads the grid
+    uint32_t target = cus * (nw == 8 ? 2u : 5u);          // see k_step: the fit role leads the grid
     uint64_t total = 0;
     for (uint32_t t = 0; t < tiles; ++t) total += (uint64_t)chunks * (6u + (2u << c->h_tile_wcls[t]));
     std::vector<FitItem> items;
@@ -1068,39 +1108,25 @@ int build_items(nhdfit_ctx* c, uint32_t nw, bool batch_find = false) {
     // for speed only), so every tile gets a multiple of 8 blocks and block j of a tile works inside eighth j % 8 of the
     // node axis: an XCD's L2 then only ever sees its eighth of the node records (0.7 MB at 65 536 nodes instead of all
     // 5.5 MB of the three row widths + busy times - more than the 4 MB an XCD has), re-read once per pod tile.
-    static const bool xcd_items = !(tune_env("NHDFIT_XCD_ITEMS") && atoi(tune_env("NHDFIT_XCD_ITEMS")) == 0);
     // ... unless the shard's records fit any XCD's L2 several times over (config 5's shard: 32 768 nodes, 1.8 MB with all three row
     // widths and the busy times): then there is nothing to partition for, and a batch of many tiles is better served by FEW, LONG
     // blocks per tile - every fit block stages the tile's hot section and derives its pair tables first (config 5: 35-50 KB), and
     // 2 300 blocks of eight chunks per wavefront spent a fifth of the step doing that.
     const uint64_t rec_bytes = (uint64_t)chunks * 64u * (16u * (c->max_wcls + 1u) + 8u);
     const bool small_shard = rec_bytes <= (2u << 20);
-    if (small_shard && nw == 8 && !c->fit_blocks) target = cus;          // (config 5 shard x 16 384 pods: 256 blocks 44.9 us per step, 512: 45.9, 1 024: 47.6, 2 048: 51.7)
+    if (small_shard && nw == 8) target = cus;          // (config 5 shard x 16 384 pods: 256 blocks 44.9 us per step, 512: 45.9, 1 024: 47.6, 2 048: 51.7)
     // (the single-launch find of a batch, k_findn, runs 256-thread blocks: the same cut into eighths of the node axis, two pieces each)
-    const bool by_xcd = xcd_items && !c->fit_blocks && chunks >= 8u * 4u * nw && (nw == 8 || batch_find) && !small_shard;
+    const bool by_xcd = chunks >= 8u * 4u * nw && (nw == 8 || batch_find) && !small_shard;
     for (uint32_t t = 0; t < tiles; ++t) {           // staged order = widest tiles first
         const uint32_t w = c->h_tile_wcls[t];
         const uint64_t cost = (uint64_t)chunks * (6u + (2u << w));
         uint32_t nb = (uint32_t)((cost * target + total / 2) / total);
         nb = std::max(1u, std::min(nb, (chunks + nw - 1) / nw));          // at least one chunk per wavefront
-        if (small_shard && nw == 8 && !c->fit_blocks) nb = std::min(nb, 8u);   // (few tiles: as the XCD form would cut them)
+        if (small_shard && nw == 8) nb = std::min(nb, 8u);   // (few tiles: as the XCD form would cut them)
         if (by_xcd) {
-            static const uint32_t force_k = tune_env("NHDFIT_XCD_K") ? (uint32_t)atoi(tune_env("NHDFIT_XCD_K")) : 0u;   // tuning aid
-            // 8, 16 or 32 blocks per tile by its cost when one launch has the chip to itself; with two pipes the other launch's
-            // blocks fill the gaps, and fewer, longer fit blocks (less staging, fewer tails) win: 8 per tile (-3 %, profiles/r03)
-            const bool two_pipes = c->dual && !c->split && !c->role_kernels;
-            static const uint32_t force_k8 = tune_env("NHDFIT_XCD_K8") ? (uint32_t)atoi(tune_env("NHDFIT_XCD_K8")) : 0u;   // tuning aid: the widest tiles only
-            const uint32_t k = force_k8 && w >= 2 ? force_k8 : force_k ? force_k : batch_find ? 2u : two_pipes ? 1u : nb <= 11 ? 1u : nb <= 23 ? 2u : 4u;
-            // tuning aid (NHDFIT_FIT_HALF = mask of row-width classes): FOUR blocks for a tile of such a class, a quarter of the node axis each -
-            // half as many stagings and pair-table derivations per tile, twice the chunks per wavefront.  Two such tiles share eight
-            // consecutive blocks (quarter q of the first on XCD q, of the second on XCD 4 + q); an odd one out gets its eight.
-            static const uint32_t half_mask = tune_env("NHDFIT_FIT_HALF") ? (uint32_t)atoi(tune_env("NHDFIT_FIT_HALF")) : 0u;
-            const bool next_same = t + 1 < tiles && c->h_tile_wcls[t + 1] == w;
-            if (!batch_find && k == 1 && (half_mask >> w & 1u) && (items.size() % 8 == 4 || next_same)) {
-                for (uint32_t q = 0; q < 4; ++q)
-                    items.push_back(FitItem{t, w, (uint32_t)((uint64_t)chunks * q / 4), (uint32_t)((uint64_t)chunks * (q + 1) / 4)});
-                continue;
-            }
+            // the step: 8 blocks per tile - the other pipes' launches fill the gaps, and fewer, longer fit blocks (less staging, fewer
+            // tails) beat 16 or 32 by 3 % (profiles/r03); the single-launch find of a batch has the chip to itself: 16
+            const uint32_t k = batch_find ? 2u : 1u;
             for (uint32_t j = 0; j < 8 * k; ++j) {
                 const uint32_t r = (j % 8) * k + j / 8;                     // range r of 8k: the (j / 8)-th piece of eighth j % 8
                 const uint32_t lo = (uint32_t)((uint64_t)chunks * r / (8 * k)), hi = (uint32_t)((uint64_t)chunks * (r + 1) / (8 * k));
@@ -1141,11 +1167,10 @@ MapArgs make_map_args(nhdfit_ctx* c, Pipe& p, int b) {
     return m;
 }
 ShapeArgs make_shape_args(nhdfit_ctx* c, Pipe& p, int b) {
-    return ShapeArgs{p.shape_keys[b].p, p.shape_res[b].p, p.shape_slot[b].p, p.shape_list[b].p, c->asc.p,
-                     c->use_choose_tab ? c->choose_tab.p : nullptr,
-                     c->use_set_states ? SetStates{c->st_info.p, c->st_next.p, c->st_asc.p, c->st_n} : SetStates{nullptr, nullptr, nullptr, 0}};
+    return ShapeArgs{p.shape_keys[b].p, p.shape_res[b].p, p.shape_slot[b].p, p.shape_list[b].p, c->asc.p, c->choose_tab.p,
+                     SetStates{c->st_info.p, c->st_next.p, c->st_asc.p, c->st_n}};
 }
-void fill_digest_args(nhdfit_ctx* c, Pipe& p, int b, uint32_t wc_parts, uint32_t sig_parts, DigestArgs& d) {
+void fill_digest_args(nhdfit_ctx* c, Pipe& p, int b, uint32_t wc_parts, DigestArgs& d) {
     d.reqs = c->reqs.p; d.P = c->P;
     d.d = DictView{c->caps.p, c->ncls, c->group_sets.p, SigDict{c->sig_off.p, c->pool_off.p, c->pool_glimit.p, c->cc.p, c->nsig}, c->sig_flat.p, c->flat_words,
                    c->sig_flat2.p, c->flat2_words};
@@ -1153,8 +1178,10 @@ void fill_digest_args(nhdfit_ctx* c, Pipe& p, int b, uint32_t wc_parts, uint32_t
     d.pitch = c->pitch; d.tabs = p.tabs[b].p; d.hdr = p.hdr[b].p; d.score = p.score[b].p;
     d.xcls = c->xcls.p; d.nx = c->xnx.p;
     d.wc_parts = wc_parts;
-    d.sig_parts = sig_parts;
-    const bool listed = c->sig_use_on && !c->all_sigs && c->sig_use_nx == c->nx && c->nx != 0;
+    // One block per tile for the signature rows: sharing them among several blocks with a last-arriver hand-over took config 5's
+    // step from 62 to 330 us (the last block derives the X rows from the others' rows past its L1, profiles/r03)
+    d.sig_parts = 1u;
+    const bool listed = !c->all_sigs && c->sig_use_nx == c->nx && c->nx != 0;
     d.sig_list = listed ? c->sig_use.p : nullptr;
     d.n_sig_list = listed ? c->n_sig_use : 0;
     d.count = p.dig_count.p;
@@ -1181,8 +1208,8 @@ void fill_fit_args(nhdfit_ctx* c, Pipe& p, int bf, double now, FitArgs& f, bool 
 }
 
 // One launch of the step kernel with every role that has work (see k_step).  `with_fit`: the fit role for step
-// n_fit plus the digest of step n_fit + 1; `flushing`: nothing new will follow, drain the mapping phases.
-int launch_step(nhdfit_ctx* c, Pipe& p, bool with_fit, bool with_digest, double now, bool flushing) {
+// n_fit plus the digest of step n_fit + 1.
+int launch_step(nhdfit_ctx* c, Pipe& p, bool with_fit, bool with_digest, double now) {
     const uint32_t P = c->P, tiles = (P + kTile - 1) / kTile;
     const uint32_t chunks = (c->n + 63) / 64;
     const bool big = c->geom_big;
@@ -1200,7 +1227,7 @@ int launch_step(nhdfit_ctx* c, Pipe& p, bool with_fit, bool with_digest, double 
     StepArgs a;
     memset(&a, 0, sizeof a);
     a.shapes_P = P;
-    a.side_prio = c->side_prio;
+    a.side_prio = 1;                                            // the side roles issue ahead of the fit role's wavefronts (settled in round 2)
     auto map_args = [&](int b) { return make_map_args(c, p, b); };
     auto shape_args = [&](int b) { return make_shape_args(c, p, b); };
     // mapping phases of earlier steps: each advances by at most one step per launch
@@ -1212,15 +1239,12 @@ int launch_step(nhdfit_ctx* c, Pipe& p, bool with_fit, bool with_digest, double 
         }
         if (p.n_chosen < p.n_shaped) {
             a.choose = shape_args((int)(p.n_chosen % kBufs));
-            // wavefront = tile, lane = shape (NHDFIT_CHOOSE_LANES=0: a wavefront per shape, 16 x the blocks - tuning aid)
-            static const bool lanes_off = tune_env("NHDFIT_CHOOSE_LANES") && atoi(tune_env("NHDFIT_CHOOSE_LANES")) == 0;
-            const bool lanes = !lanes_off;
-            a.choose_lanes = lanes ? 1u : 0u;
-            a.nb_choose = lanes ? (tiles + nw - 1) / nw : (tiles * c->choose_split + nw - 1) / nw; did_choose = true;
+            a.choose_lanes = 1u;                                // wavefront = tile, lane = shape: a wavefront per shape took 16 x the blocks (round 2)
+            a.nb_choose = (tiles + nw - 1) / nw; did_choose = true;
         }
         // scores of step s are final once its fit launch (and, sharded, its all-reduce) is done; sharded runs give
         // the all-reduce one launch of slack so that it overlaps the next fit instead of stalling the stream
-        const uint64_t ready = c->comm && !flushing && p.n_fit ? p.n_fit - 1 : p.n_fit;
+        const uint64_t ready = c->comm && p.n_fit ? p.n_fit - 1 : p.n_fit;
         if (p.n_shaped < ready) {
             const int b = (int)(p.n_shaped % kBufs);
             if (c->comm) HIPCHK(c, hipStreamWaitEvent(c->streams.use(p.k), p.ev_red[b], 0));
@@ -1231,27 +1255,22 @@ int launch_step(nhdfit_ctx* c, Pipe& p, bool with_fit, bool with_digest, double 
             a.shapes_m = map_args(b); a.shapes_h = shape_args(b); a.nb_shapes = (P + block / 4 - 1) / (block / 4); did_shapes = true;
         }
     }
-    with_digest = with_digest && p.n_dig <= p.n_fit + (with_fit ? 1 : 0) + (c->split ? 1 : 0);   // at most one step ahead of the fit
+    with_digest = with_digest && p.n_dig <= p.n_fit + (with_fit ? 1 : 0);   // at most one step ahead of the fit
     if (with_digest) {
         const int b = (int)(p.n_dig % kBufs);                              // the next undigested step
         DigestArgs& d = a.digest;
-        // (two pipes: two blocks per tile for the CPU rows instead of four - the digest's latency hides behind the other launch, its block slots do not: -3 %)
-        static const uint32_t wc_env = tune_env("NHDFIT_WC_PARTS") && atoi(tune_env("NHDFIT_WC_PARTS")) >= 1 ? (uint32_t)atoi(tune_env("NHDFIT_WC_PARTS")) : 0u;   // tuning aid
-        const uint32_t wc_parts = wc_env ? wc_env : (c->dual && !c->split && !c->role_kernels) ? 2u : kWcPartsDefault;
-        // One block per tile for the signature rows.  Sharing them among up to four blocks with a last-arriver hand-over
-        // (NHDFIT_SIG_PARTS=<n> in the tuning build) was measured on config 5's 272 signatures in round 3: the step went from 62
-        // to 330 us - the last block derives the X rows from the others' rows past its L1, three dependent 8-byte loads per
-        // (class, assignment), and that costs far more than the signature walk it parallelises (profiles/r03)
-        static const uint32_t force_sp = tune_env("NHDFIT_SIG_PARTS") ? (uint32_t)atoi(tune_env("NHDFIT_SIG_PARTS")) : 0u;   // tuning aid
-        fill_digest_args(c, p, b, wc_parts, force_sp ? std::min(force_sp, 8u) : 1u, d);
-        a.nb_digest = tiles * (d.sig_parts + wc_parts);
+        // two blocks per tile for the CPU rows, not the four of the single-launch finds: the digest's latency hides behind the other
+        // pipes' launches, its block slots do not (-3 %, profiles/r03)
+        constexpr uint32_t wc_parts = 2;
+        fill_digest_args(c, p, b, wc_parts, d);
+        a.nb_digest = tiles * (1u + wc_parts);
     }
     uint32_t nb_fit = 0;
     int bf = -1;
     if (with_fit) {
         bf = (int)(p.n_fit % kBufs);
         if (c->want_bitmap) HIPCHK(c, p.nm.reserve((size_t)tiles * chunks * 64));
-        fill_fit_args(c, p, bf, now, a.fit, !c->x_spill && !c->role_kernels && !c->split);   // (pair tables: the fused launch only)
+        fill_fit_args(c, p, bf, now, a.fit, !c->x_spill);      // (pair tables wherever the class rows do not spill)
         nb_fit = c->n_items;
     }
     a.nb_fit = nb_fit;
@@ -1263,16 +1282,13 @@ int launch_step(nhdfit_ctx* c, Pipe& p, bool with_fit, bool with_digest, double 
     const size_t map_lds = big ? map_lds_bytes<512>() : map_lds_bytes<256>();
     if ((a.nb_shapes || a.nb_finish) && map_lds > lds) lds = map_lds;
 
-    // HIP-event timing is sampled (every 8th fit launch; every digest-only launch)
-    if (with_fit && (int64_t)p.n_fit == c->role_step) {
-        HIPCHK(c, c->role_clock.reserve(32));
-        unsigned long long init[32] = {0};
-        for (int k = 0; k < 5; ++k) { init[2 * k] = ~0ull; init[2 * k + 1] = 0; }
-        HIPCHK(c, hipMemcpyAsync(c->role_clock.p, init, sizeof init, hipMemcpyHostToDevice, c->streams.use(p.k)));
-        HIPCHK(c, c->streams.wait(p.k));
+    const bool clocks = kTuning && with_fit && (int64_t)p.n_fit == c->role_step;   // tuning aid (NHDFIT_ROLE_TIMES): the roles' windows on the device clock
+    if (clocks) {
+        TRY(arm_role_clock(c, p.k, 5));
         a.role_clock = c->role_clock.p;
         a.fit.clk = c->role_clock.p + 16;                  // per-block phases of the fit role (FitArgs::clk)
     }
+    // HIP-event timing is sampled (every 8th fit launch; every digest-only launch)
     const bool timed = (with_fit && (p.n_fit < 2 || (p.n_fit & 7) == 0)) || (!with_fit && with_digest);
     if (timed && c->ev_pending == kEventRing) { int rc = drain_events(c); if (rc) return rc; }
     static const bool enq_prof = tune_env("NHDFIT_ENQ_PROF") != nullptr;
@@ -1283,22 +1299,7 @@ int launch_step(nhdfit_ctx* c, Pipe& p, bool with_fit, bool with_digest, double 
     if (c->x_spill) {               // more node classes than LDS rows: the variant whose fit role reads the rest from global memory
         if (big) hipLaunchKernelGGL((k_step<512, true>), dim3(grid), dim3(512), lds, c->streams.use(p.k), a);
         else     hipLaunchKernelGGL((k_step<256, true>), dim3(grid), dim3(256), lds, c->streams.use(p.k), a);
-    } else
-#ifdef NHDFIT_TUNING         // (role_kernels / split are switched by the tuning build's environment only: never set in libnhdfit.so)
-    if (c->role_kernels) {
-        const uint32_t nb[5] = {a.nb_choose, a.nb_shapes, a.nb_finish, a.nb_digest, nb_fit};
-        if (nb[0]) hipLaunchKernelGGL((k_role<512, 0>), dim3(nb[0]), dim3(512), 0, c->streams.use(p.k), a);
-        if (nb[1]) hipLaunchKernelGGL((k_role<512, 1>), dim3(nb[1]), dim3(512), map_lds_bytes<512>(), c->streams.use(p.k), a);
-        if (nb[2]) hipLaunchKernelGGL((k_role<512, 2>), dim3(nb[2]), dim3(512), map_lds_bytes<512>(), c->streams.use(p.k), a);
-        if (nb[3]) hipLaunchKernelGGL((k_role<512, 3>), dim3(nb[3]), dim3(512), kDigestLds, c->streams.use(p.k), a);
-        if (nb[4]) hipLaunchKernelGGL((k_role<512, 4>), dim3(nb[4]), dim3(512), lds, c->streams.use(p.k), a);
-    } else
-    if (grid == nb_fit && c->split) {
-        if (big) hipLaunchKernelGGL((k_fit_only<512>), dim3(grid), dim3(512), lds, c->streams.use(p.k), a.fit);
-        else     hipLaunchKernelGGL((k_fit_only<256>), dim3(grid), dim3(256), lds, c->streams.use(p.k), a.fit);
-    } else
-#endif
-    if (big) hipLaunchKernelGGL((k_step<512>), dim3(grid), dim3(512), lds, c->streams.use(p.k), a);
+    } else if (big) hipLaunchKernelGGL((k_step<512>), dim3(grid), dim3(512), lds, c->streams.use(p.k), a);
     else     hipLaunchKernelGGL((k_step<256>), dim3(grid), dim3(256), lds, c->streams.use(p.k), a);
     HIPCHK(c, hipGetLastError());
     if (enq_prof) c->enq_launch_us += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_l0).count();
@@ -1321,22 +1322,9 @@ int launch_step(nhdfit_ctx* c, Pipe& p, bool with_fit, bool with_digest, double 
         c->ev_kind[c->ev_pending++] = with_fit ? 0 : 1;
         if (enq_prof) c->enq_events_us += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_e1).count();
     }
-    if (a.role_clock) {
-        unsigned long long t[32];
-        HIPCHK(c, c->streams.wait(p.k));
-        HIPCHK(c, hipMemcpy(t, c->role_clock.p, sizeof t, hipMemcpyDeviceToHost));
-        if (t[24]) {
-            const double nb = (double)t[24];
-            fprintf(stderr, "[nhdfit] step %lld fit blocks (%llu): mean / latest after the block's start - staged %.2f / %.2f, pair table %.2f / %.2f, sweep done %.2f / %.2f, "
-                            "scores out %.2f / %.2f us\n", (long long)c->role_step, t[24], t[16] * 0.01 / nb, t[17] * 0.01, t[18] * 0.01 / nb, t[19] * 0.01,
-                    t[20] * 0.01 / nb, t[21] * 0.01, t[22] * 0.01 / nb, t[23] * 0.01);
-        }
-        unsigned long long first = ~0ull;
-        for (int k = 0; k < 5; ++k) first = t[2 * k] < first ? t[2 * k] : first;
-        static const char* names[5] = {"choose", "shapes", "finish", "digest", "fit"};
-        for (int k = 0; k < 5; ++k)
-            if (t[2 * k + 1]) fprintf(stderr, "[nhdfit] step %lld role %-6s: first block starts +%.2f us, last block ends +%.2f us\n",
-                                      (long long)c->role_step, names[k], (t[2 * k] - first) * 0.01, (t[2 * k + 1] - first) * 0.01);
+    if (clocks) {
+        const std::string line = "[nhdfit] step " + std::to_string(c->role_step) + " role %-6s: first block starts +%.2f us, last block ends +%.2f us\n";
+        TRY(report_role_clock(c, p.k, 5, line.c_str()));
     }
     p.n_finished += did_finish; p.n_chosen += did_choose; p.n_shaped += did_shapes;
     if (with_digest) p.n_dig++;
@@ -1357,14 +1345,12 @@ int launch_step(nhdfit_ctx* c, Pipe& p, bool with_fit, bool with_digest, double 
         p.n_fit++;
         // no mapping roles for this step (output switched off, or only 4-group pods): nothing to catch up on later
         if (!small_map) p.n_shaped = p.n_chosen = p.n_finished = p.n_fit;
-        c->stats.evals_last = (uint64_t)P * c->n;
         // algorithmic bytes of the step, SURVEY.md section 8(d): ceil(P/T) * N * B_node + P * B_req + P * N / 8 + 8 * P
         // with T = 64 pods per tile, B_node = 24 (the 16-byte node record + the 8-byte busy time every tile streams),
         // B_req = 128; the P * N / 8 term is the node-major verdict matrix (dropped when that output is switched off)
-        c->stats.bytes_last = (uint64_t)tiles * c->n * 24ull + (uint64_t)P * sizeof(nhdfit_req) +
-                              (c->want_bitmap ? (uint64_t)tiles * chunks * 64ull * 8ull : 0ull) + (uint64_t)P * 8ull;
-        c->stats.nodes = c->n; c->stats.nsig = c->nsig; c->stats.ncls = c->ncls; c->stats.lds_bytes = c->lds_bytes;
-        c->stats.pipes = c->dual && !c->split && !c->role_kernels ? (uint32_t)c->npipes : 1u;
+        store_find_stats(c, (uint64_t)P * c->n, (uint64_t)tiles * c->n * 24ull + (uint64_t)P * sizeof(nhdfit_req) +
+                                                (c->want_bitmap ? (uint64_t)tiles * chunks * 64ull * 8ull : 0ull) + (uint64_t)P * 8ull);
+        c->stats.pipes = (uint32_t)c->npipes;
     }
     return NHDFIT_OK;
 }
@@ -1391,15 +1377,8 @@ int convert_rows_t(nhdfit_ctx* c, Pipe& p) {
 
 int flush_pipeline(nhdfit_ctx* c) {
     if (!c->P || !c->want_map || c->n_big_pods >= c->P) return NHDFIT_OK;
-    static const bool role_drain = tune_env("NHDFIT_ROLE_DRAIN") != nullptr;   // tuning aid: drain with role launches, as the steps ran
     const uint32_t tiles = (c->P + kTile - 1) / kTile;
     for (Pipe& p : c->pipe) {
-        if (role_drain || c->role_kernels || c->split) {
-            while (p.n_finished < p.n_fit) {
-                TRY(launch_step(c, p, false, false, 0.0, true));
-            }
-            continue;
-        }
         // the steps whose mapping phases have not all run: mapped from their scores in one launch (k_map_tiles, step_map.h)
         while (p.n_finished < p.n_fit) {
             DrainArgs a;
@@ -1461,8 +1440,6 @@ static int enqueue_step(nhdfit_ctx* c, double now) {
         // others' sweep), 256-thread blocks for small problems so that the grid still covers the chip
         const uint32_t tiles = (c->P + kTile - 1) / kTile, chunks = (c->n + 63) / 64;
         c->geom_big = (uint64_t)tiles * ((chunks + 31) / 32) >= (uint32_t)c->prop.multiProcessorCount;
-        if (const char* b = tune_env("NHDFIT_BLOCK")) c->geom_big = atoi(b) >= 512;      // tuning aid
-        if (c->role_kernels) c->geom_big = true;
         // How many launches in flight (profiles/r04/pipes_*.log).  A third one covers long latency chains inside a launch: with a
         // large dictionary the digest role is one (config 5, 151 signatures: 15.9 -> 10.9 us per step of 2 048 pods).  Where the
         // fit role fills the launch (config 4) it buys 3 % in steady state and costs as much in a short run, whose end waits for
@@ -1471,9 +1448,9 @@ static int enqueue_step(nhdfit_ctx* c, double now) {
         static const int force_pipes = tune_env("NHDFIT_PIPES") ? atoi(tune_env("NHDFIT_PIPES")) : 0;   // tuning aid
         c->npipes = force_pipes >= 1 && force_pipes <= kPipes ? force_pipes : (c->geom_big && c->nsig > 64) ? 3 : 2;
     }
-    // step k of a staged batch runs on pipe k % 2 (sharded runs too: the all-reduces of both pipes go to the one reduce
-    // stream in step order, the same order on every rank); the profiling forms stay on pipe 0
-    const int which = c->dual && !c->split && !c->role_kernels ? (int)(c->n_enq % (uint64_t)c->npipes) : 0;
+    // step k of a staged batch runs on pipe k % npipes (sharded runs too: the all-reduces of all pipes go to the one reduce
+    // stream in step order, the same order on every rank)
+    const int which = (int)(c->n_enq % (uint64_t)c->npipes);
     Pipe& p = c->pipe[which];
     c->n_enq++;
     c->last_pipe = which;
@@ -1481,13 +1458,9 @@ static int enqueue_step(nhdfit_ctx* c, double now) {
     // records first - new node classes put the digests that ran ahead back (ensure_records), and they are redone below
     TRY(ensure_records(c));
     if (p.n_dig <= p.n_fit) {                        // this pipe's first step after staging (or after such a change): its digest has not run yet
-        TRY(launch_step(c, p, false, true, now, false));
+        TRY(launch_step(c, p, false, true, now));
     }
-    if (c->split) {                                  // profiling aid: side roles and fit role as two launches
-        TRY(launch_step(c, p, false, true, now, false));
-        return launch_step(c, p, true, false, now, false);
-    }
-    return launch_step(c, p, true, true, now, false);
+    return launch_step(c, p, true, true, now);
 }
 
 int nhdfit_sync(nhdfit_ctx* c) {
@@ -1568,8 +1541,7 @@ Find1Args lone_find_args(nhdfit_ctx* c, double now, uint32_t seq, bool want_map)
     a1.d = DictView{c->caps.p, c->ncls, c->group_sets.p, SigDict{c->sig_off.p, c->pool_off.p, c->pool_glimit.p, c->cc.p, c->nsig}, c->sig_flat.p, c->flat_words, nullptr, 0};
     a1.nsig = c->nsig; a1.fc_dim = c->max_cores + 1; a1.fg_dim = c->max_gpus + 1; a1.ngs = c->ngs;
     a1.chunks = chunks;
-    static const uint32_t lone_nb = tune_env("NHDFIT_FIND_BLOCKS") ? (uint32_t)atoi(tune_env("NHDFIT_FIND_BLOCKS")) : 0u;   // tuning aid
-    a1.nb = std::max(1u, std::min(chunks, lone_nb ? lone_nb : std::min((chunks + 7) / 8, (uint32_t)c->prop.multiProcessorCount)));   // two chunks per wavefront
+    a1.nb = std::max(1u, std::min((chunks + 7) / 8, (uint32_t)c->prop.multiProcessorCount));   // two chunks per wavefront
     a1.busy_from = busy_threshold(now);
     a1.cand = c->use_cand ? c->cand.p : nullptr;
     a1.sync = c->find_sync.p; a1.host = h; a1.seq = seq; a1.want_map = want_map ? 1u : 0u;
@@ -1613,8 +1585,8 @@ int find_small(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, double now, co
         TRY(drain_events(c));
     }
     Pipe& p = c->pipe[0];
-    for (Pipe& q : c->pipe) q.n_dig = q.n_fit = q.n_shaped = q.n_chosen = q.n_finished = 0;
-    c->n_enq = 0; c->last_pipe = 0; c->n_items = 0; c->n_big_pods = 0;
+    reset_step_counters(c);
+    c->n_items = 0; c->n_big_pods = 0;
     // one pod: no table image at all (k_find1) when the dictionary's 16-bit stream and its signature count fit the block's LDS
     const bool lone = P == 1 && c->lone_pod && c->flat_words && c->flat_words <= kDictLdsWords && c->nsig <= kLoneMaxSigs;
     c->P = P;                                                   // (for the layout / argument helpers; nothing stays staged: reset below)
@@ -1632,26 +1604,23 @@ int find_small(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, double now, co
 
     FindHost* h = c->find_host;
     memcpy(h->reqs, reqs, (size_t)P * sizeof *reqs);
-    uint32_t seq = ++c->find_seq;
-    if (seq == 0u || seq == kFindAborted) seq = c->find_seq = 1u;
+    const uint32_t seq = next_find_seq(c);
     Find1Args a1;
     memset(&a1, 0, sizeof a1);
     if (lone) a1 = lone_find_args(c, now, seq, map_out != nullptr);
     FindArgs a;
     memset(&a, 0, sizeof a);
     a.s.shapes_P = P;
-    static const uint32_t find_wc = tune_env("NHDFIT_FIND_WC_PARTS") && atoi(tune_env("NHDFIT_FIND_WC_PARTS")) >= 1 ? (uint32_t)atoi(tune_env("NHDFIT_FIND_WC_PARTS")) : kWcPartsDefault;   // tuning aid
-    fill_digest_args(c, p, 0, find_wc, 1u, a.s.digest);
+    fill_digest_args(c, p, 0, kWcPartsDefault, a.s.digest);     // (the digest is on the call's critical path: the CPU rows cut four ways)
     a.s.digest.reqs = h->reqs;
-    a.s.nb_digest = 1u + find_wc;
+    a.s.nb_digest = 1u + kWcPartsDefault;
     fill_fit_args(c, p, 0, now, a.s.fit);
     a.s.fit.nm = nullptr; a.s.fit.items = nullptr; a.s.fit.dbg_skip = 0;
     constexpr uint32_t nw = 4;                                  // 256-thread blocks: a wavefront per chunk where the cluster is small enough
     // Few, longer fit blocks: every block stages the tile's table rows (tens of KB) before its first chunk and waits for the digest
     // on one counter - measured at 65 536 nodes (profiles/r03): 256 blocks 107 us per call, 64 blocks 54, 32 blocks 50.  Eight
     // chunks per wavefront, at most one block per CU.
-    static const uint32_t force_nb = tune_env("NHDFIT_FIND_BLOCKS") ? (uint32_t)atoi(tune_env("NHDFIT_FIND_BLOCKS")) : 0u;   // tuning aid
-    a.s.nb_fit = std::max(1u, std::min((chunks + nw - 1) / nw, force_nb ? force_nb : std::min((chunks + 8 * nw - 1) / (8 * nw), (uint32_t)c->prop.multiProcessorCount)));
+    a.s.nb_fit = std::max(1u, std::min((chunks + 8 * nw - 1) / (8 * nw), (uint32_t)c->prop.multiProcessorCount));
     a.s.finish_m = make_map_args(c, p, 0);                      // the mapping tail (map_one_tile): requests in, mappings out of the host block
     a.s.finish_m.reqs = h->reqs; a.s.finish_m.tile_wcls = nullptr; a.s.finish_m.out = h->maps;
     a.s.finish_h = make_shape_args(c, p, 0);
@@ -1661,10 +1630,7 @@ int find_small(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, double now, co
     lds = std::max(lds, std::max(kDigestLds, map_tile_lds_bytes<256>()));
     const bool clocks = kTuning && c->role_step >= 0;           // tuning aid (NHDFIT_ROLE_TIMES): the phases of the launch on the device clock
     if (clocks) {
-        HIPCHK(c, c->role_clock.reserve(10));
-        unsigned long long init[10];
-        for (int k = 0; k < 5; ++k) { init[2 * k] = ~0ull; init[2 * k + 1] = 0; }
-        HIPCHK(c, hipMemcpy(c->role_clock.p, init, sizeof init, hipMemcpyHostToDevice));
+        TRY(arm_role_clock(c, 0, 5));
         a.s.role_clock = c->role_clock.p;
         a1.role_clock = c->role_clock.p;
     }
@@ -1683,16 +1649,9 @@ int find_small(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, double now, co
     }
     if (clocks) {
         const double us_seen = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_launch).count();
-        unsigned long long t[10];
-        HIPCHK(c, c->streams.wait(0));
-        HIPCHK(c, hipMemcpy(t, c->role_clock.p, sizeof t, hipMemcpyDeviceToHost));
-        unsigned long long first = ~0ull;
-        for (int k = 0; k < 5; ++k) first = t[2 * k] < first ? t[2 * k] : first;
-        static const char* names[5] = {"choose", "shapes", "finish", "digest", "fit"};
         fprintf(stderr, "[nhdfit] single-launch find%s: %u fit blocks, results seen %.1f us after the launch call began (host prep %.1f us)\n", lone ? " (lone pod, no tables)" : "", lone ? a1.nb : a.s.nb_fit, us_seen,
                 std::chrono::duration<double, std::micro>(t_launch - t0).count());
-        for (int k = 0; k < 5; ++k)
-            if (t[2 * k + 1]) fprintf(stderr, "[nhdfit]   %-6s: +%.2f us .. +%.2f us\n", names[k], (t[2 * k] - first) * 0.01, (t[2 * k + 1] - first) * 0.01);
+        TRY(report_role_clock(c, 0, 5, "[nhdfit]   %-6s: +%.2f us .. +%.2f us\n"));
     }
     if (c->comm) {
         // sharded: every rank ran the launch on its shard and mapped its own winner; one all-reduce(max) of the packed scores
@@ -1719,9 +1678,7 @@ int find_small(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, double now, co
     }
     if (score_out) memcpy(score_out, h->score, (size_t)P * 8);
     if (map_out) memcpy(map_out, h->maps, (size_t)P * sizeof(nhdfit_mapping));
-    c->stats.evals_last = (uint64_t)P * c->n;
-    c->stats.bytes_last = (uint64_t)c->n * 24ull + (uint64_t)P * sizeof(nhdfit_req) + (uint64_t)P * 8ull;
-    c->stats.nodes = c->n; c->stats.nsig = c->nsig; c->stats.ncls = c->ncls; c->stats.lds_bytes = c->lds_bytes;
+    store_find_stats(c, (uint64_t)P * c->n, (uint64_t)c->n * 24ull + (uint64_t)P * sizeof(nhdfit_req) + (uint64_t)P * 8ull);
     c->stats.small_finds++;
     return NHDFIT_OK;
 }
@@ -1746,8 +1703,8 @@ int find_commit_fused(nhdfit_ctx* c, const nhdfit_req* req, double now, const ui
         TRY(drain_events(c));
     } else TRY(check_skipped_waits(c, "nhdfit_find_commit"));
     Pipe& p = c->pipe[0];
-    for (Pipe& q : c->pipe) q.n_dig = q.n_fit = q.n_shaped = q.n_chosen = q.n_finished = 0;
-    c->n_enq = 0; c->last_pipe = 0; c->n_items = 0; c->n_big_pods = 0;
+    reset_step_counters(c);
+    c->n_items = 0; c->n_big_pods = 0;
     c->P = 0;                                                   // nothing is (or stays) staged
     c->hp_rows = (uint32_t)req->hugepages_gb + 2;
     c->max_wcls = req_valid(*req) ? wclass_of(req->n_groups) : 0;
@@ -1757,8 +1714,7 @@ int find_commit_fused(nhdfit_ctx* c, const nhdfit_req* req, double now, const ui
     FindHost* h = c->find_host;
     h->reqs[0] = *req;
     h->committed = 0;
-    uint32_t seq = ++c->find_seq;
-    if (seq == 0u || seq == kFindAborted) seq = c->find_seq = 1u;
+    const uint32_t seq = next_find_seq(c);
     Find1CommitArgs a;
     memset(&a, 0, sizeof a);
     a.f = lone_find_args(c, now, seq, true);
@@ -1767,12 +1723,9 @@ int find_commit_fused(nhdfit_ctx* c, const nhdfit_req* req, double now, const ui
     a.busy_time = busy_time;
     a.prev_node = prev_node < 0 ? kNoPrevNode : (uint32_t)prev_node; a.prev_busy_time = prev_busy_time;
     const bool clocks = kTuning && c->role_step >= 0;           // tuning aid (NHDFIT_ROLE_TIMES): the phases of the launch on the device clock
-    constexpr int kSlots = kClockCommitTail + 1;
+    constexpr int kSlots = kClockCommitTail + 1;                // (the five roles' slots and the commit's)
     if (clocks) {
-        HIPCHK(c, c->role_clock.reserve(2 * kSlots));
-        unsigned long long init[2 * kSlots];
-        for (int k = 0; k < kSlots; ++k) { init[2 * k] = ~0ull; init[2 * k + 1] = 0; }
-        HIPCHK(c, hipMemcpy(c->role_clock.p, init, sizeof init, hipMemcpyHostToDevice));
+        TRY(arm_role_clock(c, 0, kSlots));
         a.f.role_clock = c->role_clock.p;
     }
     const auto t_launch = std::chrono::steady_clock::now();
@@ -1783,33 +1736,19 @@ int find_commit_fused(nhdfit_ctx* c, const nhdfit_req* req, double now, const ui
     if (seen != seq) return fail(c, NHDFIT_E_HIP, "the find-and-commit kernel ended without publishing its results");
     if (clocks) {
         const double us_seen = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_launch).count();
-        unsigned long long t[2 * kSlots];
-        HIPCHK(c, c->streams.wait(0));
-        HIPCHK(c, hipMemcpy(t, c->role_clock.p, sizeof t, hipMemcpyDeviceToHost));
-        unsigned long long first = ~0ull;
-        for (int k = 0; k < kSlots; ++k) first = t[2 * k] < first ? t[2 * k] : first;
-        static const char* names[kSlots] = {"choose", "shapes", "finish", "digest", "fit", "commit"};
         fprintf(stderr, "[nhdfit] find and commit in one launch: %u blocks, results seen %.1f us after the launch call began (host prep %.1f us)\n", a.f.nb, us_seen,
                 std::chrono::duration<double, std::micro>(t_launch - t0).count());
-        for (int k = 0; k < kSlots; ++k)
-            if (t[2 * k + 1]) fprintf(stderr, "[nhdfit]   %-6s: +%.2f us .. +%.2f us\n", names[k], (t[2 * k] - first) * 0.01, (t[2 * k + 1] - first) * 0.01);
+        TRY(report_role_clock(c, 0, kSlots, "[nhdfit]   %-6s: +%.2f us .. +%.2f us\n"));
     }
     *score_out = h->score[0];
     *map_out = h->maps[0];
-    c->stats.evals_last = c->n;
-    c->stats.bytes_last = (uint64_t)c->n * 24ull + sizeof(nhdfit_req) + 8ull;
-    c->stats.nodes = c->n; c->stats.nsig = c->nsig; c->stats.ncls = c->ncls; c->stats.lds_bytes = c->lds_bytes;
-    if (prev_node >= 0) {                                       // the correction wrote plane 4 of that node
-        const uint32_t v = (uint32_t)prev_node;
-        if (c->rec_lo == c->rec_hi) { c->rec_lo = v; c->rec_hi = v + 1; }
-        else { c->rec_lo = std::min(c->rec_lo, v); c->rec_hi = std::max(c->rec_hi, v + 1); }
-    }
+    store_find_stats(c, c->n, (uint64_t)c->n * 24ull + sizeof(nhdfit_req) + 8ull);
+    if (prev_node >= 0) mark_records_stale(c, (uint32_t)prev_node, (uint32_t)prev_node + 1);   // the correction wrote plane 4 of that node
     if (!h->committed) return h->score[0] && h->maps[0].valid ? 2 : NHDFIT_OK;
     *place_out = h->place;
     *committed = 1;
     const uint32_t node = (uint32_t)(NHDFIT_SCORE_INDEX(h->score[0]) - c->global_base);
-    if (c->rec_lo == c->rec_hi) { c->rec_lo = node; c->rec_hi = node + 1; }
-    else { c->rec_lo = std::min(c->rec_lo, node); c->rec_hi = std::max(c->rec_hi, node + 1); }
+    mark_records_stale(c, node, node + 1);
     return NHDFIT_OK;
 }
 
@@ -1819,16 +1758,9 @@ int find_commit_fused(nhdfit_ctx* c, const nhdfit_req* req, double now, const ui
 // Returns 0 = done (nothing stays staged), 1 = not eligible, nothing touched; 2 = the batch is STAGED but the launch did not run or
 // gave up: the caller goes on with nhdfit_enqueue_step / nhdfit_fetch; < 0 = error (worded).
 int find_batch(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, double now, const uint64_t* cand, uint64_t* score_out, nhdfit_mapping* map_out) {
-    if (!c->batch_find || !c->fast_find || !reqs || P <= (uint32_t)kTile || !c->nsig || !c->n || c->n_wide || c->comm || c->role_kernels || c->split) return 1;
+    if (!c->batch_find || !c->fast_find || !reqs || P <= (uint32_t)kTile || !c->nsig || !c->n || c->n_wide || c->comm) return 1;
     if (map_out && !c->want_map) return 1;
-    static const bool prof = tune_env("NHDFIT_FIND_PROF") != nullptr;      // tuning aid: host-side phase times of the call
-    auto t_prev = std::chrono::steady_clock::now();
-    auto lap = [&](const char* what) {
-        if (!prof) return;
-        const auto t1 = std::chrono::steady_clock::now();
-        fprintf(stderr, "[nhdfit] batch find P=%u %s %.1f us\n", P, what, std::chrono::duration<double, std::micro>(t1 - t_prev).count());
-        t_prev = t1;
-    };
+    PhaseTimer prof{"batch find", P};
     // sorted into tiles in the page-locked block.  What the launch reads once per block - tile classes, work items - it reads there; the
     // request records of a FEW tiles too (five digest blocks and the mapping read a tile's 8 KB over the link: cheaper than a copy
     // command's ~10 us up to a few hundred pods, dearer than the copy beyond)
@@ -1838,7 +1770,7 @@ int find_batch(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, double now, co
     const size_t tail_cap = host_reqs ? 0 : ((size_t)tiles_ * 32 + 4096) * sizeof(FitItem) + (size_t)tiles_ * 8 + 64;
     int rc = stage_requests(c, reqs, P, true, true, tail_cap);
     if (rc) return rc;
-    lap("stage");
+    prof.lap("stage");
     auto to_steps = [&]() { const int r2 = finish_deferred_copies(c); return r2 ? r2 : 2; };
     if (c->n_big_pods) return to_steps();                       // four-group pods: their set model is a kernel of its own
     if (cand && (rc = stage_cand(c, cand))) return rc;
@@ -1846,7 +1778,7 @@ int find_batch(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, double now, co
     if (c->x_spill) return to_steps();
     constexpr uint32_t nw = 4;                                  // 256-thread blocks: a tile's pods are one wavefront of the mapping tail
     if ((rc = build_items(c, nw, true))) return rc;
-    const uint32_t tiles = (P + kTile - 1) / kTile, chunks = (c->n + 63) / 64;
+    const uint32_t tiles = (P + kTile - 1) / kTile;
     Pipe& p = c->pipe[0];
     // the host block: flag word (16 bytes), P score words, P mappings
     if (P > c->findn_cap) {
@@ -1867,16 +1799,13 @@ int find_batch(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, double now, co
         HIPCHK(c, hipMemsetAsync(c->findn_sync.p, 0, (size_t)words * sizeof(uint32_t), c->streams.use(0)));
         c->findn_sync_words = words;
     }
-    uint32_t seq = ++c->find_seq;
-    if (seq == 0u || seq == kFindAborted) seq = c->find_seq = 1u;
+    const uint32_t seq = next_find_seq(c);
 
     FindNArgs a;
     memset(&a, 0, sizeof a);
     a.s.shapes_P = P;
-    static const uint32_t wc_env = tune_env("NHDFIT_FIND_WC_PARTS") && atoi(tune_env("NHDFIT_FIND_WC_PARTS")) >= 1 ? (uint32_t)atoi(tune_env("NHDFIT_FIND_WC_PARTS")) : 0u;   // tuning aid
-    const uint32_t wc_parts = wc_env ? wc_env : kWcPartsDefault;   // (the digest is on the call's critical path here: the CPU rows cut four ways, as the one-tile find cuts them)
-    fill_digest_args(c, p, 0, wc_parts, 1u, a.s.digest);
-    a.dig_parts = 1u + wc_parts;
+    fill_digest_args(c, p, 0, kWcPartsDefault, a.s.digest);     // (the digest is on the call's critical path here: the CPU rows cut four ways, as the one-tile find cuts them)
+    a.dig_parts = 1u + kWcPartsDefault;
     a.s.nb_digest = tiles * a.dig_parts;
     a.nb_lead = (a.s.nb_digest + 7u) & ~7u;
     fill_fit_args(c, p, 0, now, a.s.fit, true);
@@ -1908,11 +1837,11 @@ int find_batch(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, double now, co
     a.sync = c->findn_sync.p; a.host_score = h_score; a.host_flag = h_flag; a.seq = seq;
     size_t lds = lds_slice(c->lds_bytes) + (size_t)nw * 64 * sizeof(unsigned long long);
     lds = std::max(lds, std::max(kDigestLds, map_tile_lds_bytes<256>()));
-    lap("records, items, arguments");
+    prof.lap("records, items, arguments");
     const auto t_launch = std::chrono::steady_clock::now();
     hipLaunchKernelGGL((k_findn<256>), dim3(a.nb_lead + a.s.nb_fit), dim3(256), lds, c->streams.use(0), a);
     HIPCHK(c, hipGetLastError());
-    lap("launch call");
+    prof.lap("launch call");
     uint32_t seen = 0;
     TRY(poll_word(c, h_flag, seq, kFindAborted, t_launch, 2000, 0, seen));
     if (seen != seq) {                                          // the launch gave up on a wait: counters back to zero, staged path
@@ -1922,60 +1851,49 @@ int find_batch(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, double now, co
         c->n_items = 0;                                         // (the step's own work items: 512-thread blocks)
         return to_steps();
     }
-    lap("poll");
+    prof.lap("poll");
     if (score_out) for (uint32_t i = 0; i < P; ++i) score_out[c->perm[i]] = h_score[i];
     if (map_out) for (uint32_t i = 0; i < P; ++i) map_out[c->perm[i]] = h_maps[i];
-    lap("results to the caller's order");
-    c->stats.evals_last = (uint64_t)P * c->n;
-    c->stats.bytes_last = (uint64_t)tiles * c->n * 24ull + (uint64_t)P * sizeof(nhdfit_req) + (uint64_t)P * 8ull;
-    c->stats.nodes = c->n; c->stats.nsig = c->nsig; c->stats.ncls = c->ncls; c->stats.lds_bytes = c->lds_bytes;
+    prof.lap("results to the caller's order");
+    store_find_stats(c, (uint64_t)P * c->n, (uint64_t)tiles * c->n * 24ull + (uint64_t)P * sizeof(nhdfit_req) + (uint64_t)P * 8ull);
     c->stats.batch_finds++;
     c->P = 0; c->n_items = 0;                                   // nothing stays staged for nhdfit_enqueue_step / nhdfit_fetch
     c->streams.pipe0_drained_by_its_last_word();                // (the word came behind everything this call put on the stream)
-    (void)chunks;
     return NHDFIT_OK;
 }
 }  // namespace
 
 int nhdfit_find(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, double now, const uint64_t* cand,
                 uint64_t* score_out, uint64_t* bitmap_out, nhdfit_mapping* map_out) {
-    static const bool prof = tune_env("NHDFIT_FIND_PROF") != nullptr;      // tuning aid: host-side phase times of the call
-    auto t0 = std::chrono::steady_clock::now();
-    auto lap = [&](const char* what) {
-        if (!prof) return;
-        const auto t1 = std::chrono::steady_clock::now();
-        fprintf(stderr, "[nhdfit] find P=%u %s %.1f us\n", P, what, std::chrono::duration<double, std::micro>(t1 - t0).count());
-        t0 = t1;
-    };
+    PhaseTimer prof{"find", P};
     if (c && !bitmap_out) {
         const int rs = find_small(c, reqs, P, now, cand, score_out, map_out);
-        if (rs <= 0) { lap("single launch"); return rs; }
+        if (rs <= 0) { prof.lap("single launch"); return rs; }
     }
     int rc;
     bool staged = false;
     if (c && !bitmap_out) {
         const int rb = find_batch(c, reqs, P, now, cand, score_out, map_out);
-        if (rb <= 0) { lap("single launch, batch"); return rb; }
+        if (rb <= 0) { prof.lap("single launch, batch"); return rb; }
         staged = rb == 2;                                       // (the launch did not run: the staged batch takes the steps' path)
     }
     if (!staged) {
         rc = nhdfit_stage_requests(c, reqs, P);
         if (rc) return rc;
     }
-    lap("stage");
+    prof.lap("stage");
     if (cand && (rc = stage_cand(c, cand))) return rc;
     if ((rc = nhdfit_enqueue_step(c, now))) return rc;
-    lap("enqueue");
-    if (prof) { if ((rc = flush_pipeline(c))) return rc; lap("flush-launches"); if ((rc = nhdfit_sync(c))) return rc; lap("sync"); }
+    prof.lap("enqueue");
+    if (prof.on()) { if ((rc = flush_pipeline(c))) return rc; prof.lap("flush-launches"); if ((rc = nhdfit_sync(c))) return rc; prof.lap("sync"); }
     rc = nhdfit_fetch(c, score_out, bitmap_out, map_out);
-    lap("fetch");
+    prof.lap("fetch");
     return rc;
 }
 
 namespace {
 MapTables map_tables(nhdfit_ctx* c) {
-    return MapTables{c->asc.p, c->use_choose_tab ? c->choose_tab.p : nullptr,
-                     c->use_set_states ? SetStates{c->st_info.p, c->st_next.p, c->st_asc.p, c->st_n} : SetStates{nullptr, nullptr, nullptr, 0}};
+    return MapTables{c->asc.p, c->choose_tab.p, SetStates{c->st_info.p, c->st_next.p, c->st_asc.p, c->st_n}};
 }
 SigTable sig_table(nhdfit_ctx* c) { return SigTable{c->sig_keys.p, c->sig_ids.p, c->sig_mask}; }
 }  // namespace
@@ -2186,8 +2104,7 @@ int nhdfit_big_commit(nhdfit_ctx* c, uint32_t node, const nhdfit_big_req* req, c
     HIPCHK(c, hipMemcpyAsync(place_out, c->big_place.p, sizeof *place_out, hipMemcpyDeviceToHost, c->streams.use(0)));
     HIPCHK(c, c->streams.wait(0));
     if (slot < 0) {                                             // the node's records (X class, free-core counts) follow its planes
-        if (c->rec_lo == c->rec_hi) { c->rec_lo = node; c->rec_hi = node + 1; }
-        else { c->rec_lo = std::min(c->rec_lo, node); c->rec_hi = std::max(c->rec_hi, node + 1); }
+        mark_records_stale(c, node, node + 1);
     }
     return NHDFIT_OK;
 }
@@ -2394,12 +2311,10 @@ int nhdfit_schedule_batch(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, dou
         size_t seq_lds = lds_slice((size_t)tiles * 16) + lds_slice(((size_t)c->sig_mask + 1) * 8) + lds_slice(((size_t)c->sig_mask + 1) * 4) + lds_slice((size_t)P * 4) + lds_slice(tiles);
         g.lds_tables = seq_lds <= 96 * 1024;
         if (!g.lds_tables) seq_lds = 0;
-        const int seq_pods = c->seq_pods;
-        HIPCHK(c, hipFuncSetAttribute(seq_pods == 16 ? (const void*)k_seq<16> : (const void*)k_seq<8>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
+        HIPCHK(c, hipFuncSetAttribute((const void*)k_seq<16>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));   // sixteen pods per round
         const bool seq_prof = tune_env("NHDFIT_SEQ_PROF") != nullptr;
         if (seq_prof) { HIPCHK(c, c->role_clock.reserve(16)); g.prof = c->role_clock.p; }
-        if (seq_pods == 16) hipLaunchKernelGGL(k_seq<16>, dim3(1), dim3(1024), seq_lds, c->streams.use(0), g);
-        else hipLaunchKernelGGL(k_seq<8>, dim3(1), dim3(512), seq_lds, c->streams.use(0), g);
+        hipLaunchKernelGGL(k_seq<16>, dim3(1), dim3(1024), seq_lds, c->streams.use(0), g);
         HIPCHK(c, hipGetLastError());
         if (seq_prof) {
             unsigned long long t[16];
@@ -2475,12 +2390,11 @@ int nhdfit_schedule_batch(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, dou
         const size_t st_bytes = lds_slice((size_t)c->st_n * 8) + lds_slice((size_t)c->st_n * 32) + lds_slice(256 * 4);
         const size_t room96 = dyn_room < 96 * 1024 ? dyn_room : 96 * 1024, room112 = dyn_room < 112 * 1024 ? dyn_room : 112 * 1024;
         if (dyn + sig_bytes <= room96) { qa.lds_sigs = 1; dyn += sig_bytes; }
-        if (c->use_set_states && c->st_n && dyn + st_bytes <= room96) { qa.lds_states = 1; dyn += st_bytes; }
-        if (c->use_choose_tab && dyn + lds_slice(kChooseEntries) <= room112) { qa.lds_choose = 1; dyn += lds_slice(kChooseEntries); }
+        if (c->st_n && dyn + st_bytes <= room96) { qa.lds_states = 1; dyn += st_bytes; }
+        if (dyn + lds_slice(kChooseEntries) <= room112) { qa.lds_choose = 1; dyn += lds_slice(kChooseEntries); }
         HIPCHK(c, hipFuncSetAttribute(any_g4 ? (const void*)k_decide<true> : (const void*)k_decide<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
-        static const uint32_t workers = tune_env("NHDFIT_SEQ_WORKERS") ? (uint32_t)atoi(tune_env("NHDFIT_SEQ_WORKERS")) : (uint32_t)kWorkerBlocks;   // tuning aid
-        if (any_g4) hipLaunchKernelGGL(k_decide<true>, dim3(1 + (workers ? workers : 1u)), dim3(64 * kDecideWaves), dyn, c->streams.use(0), qa);
-        else hipLaunchKernelGGL(k_decide<false>, dim3(1 + (workers ? workers : 1u)), dim3(64 * kDecideWaves), dyn, c->streams.use(0), qa);
+        if (any_g4) hipLaunchKernelGGL(k_decide<true>, dim3(1 + kWorkerBlocks), dim3(64 * kDecideWaves), dyn, c->streams.use(0), qa);
+        else hipLaunchKernelGGL(k_decide<false>, dim3(1 + kWorkerBlocks), dim3(64 * kDecideWaves), dyn, c->streams.use(0), qa);
         HIPCHK(c, hipGetLastError());
         uint32_t flags[4] = {0, 0, 0, 0};
         HIPCHK(c, hipMemcpyAsync(flags, c->seq_flags.p, sizeof flags, hipMemcpyDeviceToHost, c->streams.use(0)));
@@ -2531,8 +2445,7 @@ int nhdfit_schedule_batch(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, dou
         }
     }
     if (apply && lo >= 0) {                                     // records of the committed nodes are stale
-        if (c->rec_lo == c->rec_hi) { c->rec_lo = (uint32_t)lo; c->rec_hi = (uint32_t)hi; }
-        else { c->rec_lo = std::min(c->rec_lo, (uint32_t)lo); c->rec_hi = std::max(c->rec_hi, (uint32_t)hi); }
+        mark_records_stale(c, (uint32_t)lo, (uint32_t)hi);
     }
     return NHDFIT_OK;
 }
@@ -2586,8 +2499,7 @@ int nhdfit_commit(nhdfit_ctx* c, uint32_t node, const nhdfit_req* req, const nhd
     TRY(poll_word(c, &c->commit_host->flag, seq, seq, t_launch, 500, 0, seen));
     if (seen != seq) return fail(c, NHDFIT_E_HIP, "the commit kernel ended without publishing its placement");
     *place_out = c->commit_host->place;
-    if (c->rec_lo == c->rec_hi) { c->rec_lo = node; c->rec_hi = node + 1; }
-    else { c->rec_lo = std::min(c->rec_lo, node); c->rec_hi = std::max(c->rec_hi, node + 1); }
+    mark_records_stale(c, node, node + 1);
     return NHDFIT_OK;
 }
 
@@ -2615,8 +2527,7 @@ int nhdfit_find_commit(nhdfit_ctx* c, const nhdfit_req* req, double now, const u
         hipLaunchKernelGGL(k_set_busy, dim3(1), dim3(64), 0, c->streams.use(0), c->p4.p, (uint32_t)prev_node, prev_busy_time);   // (stream order: the find follows on pipe 0)
         HIPCHK(c, hipGetLastError());
         const uint32_t v = (uint32_t)prev_node;
-        if (c->rec_lo == c->rec_hi) { c->rec_lo = v; c->rec_hi = v + 1; }
-        else { c->rec_lo = std::min(c->rec_lo, v); c->rec_hi = std::max(c->rec_hi, v + 1); }
+        mark_records_stale(c, v, v + 1);
     }
     if (rf == 1) TRY(nhdfit_find(c, req, 1, now, cand, score_out, nullptr, map_out));
     if (!*score_out || !map_out->valid) return NHDFIT_OK;       // nothing fits (or, sharded, another rank owns the winner's mapping)
@@ -2689,8 +2600,7 @@ int nhdfit_apply_deltas(nhdfit_ctx* c, const nhdfit_delta* deltas, uint32_t n, u
     HIPCHK(c, hipMemcpyAsync(st.data(), c->delta_status.p, n, hipMemcpyDeviceToHost, c->streams.use(0)));
     HIPCHK(c, c->streams.wait(0));                  // (also keeps `sorted` / `run` alive until the copies are done)
     for (uint32_t i = 0; i < n; ++i) status_out[order[i]] = st[i];
-    if (c->rec_lo == c->rec_hi) { c->rec_lo = lo; c->rec_hi = hi; }
-    else { c->rec_lo = std::min(c->rec_lo, lo); c->rec_hi = std::max(c->rec_hi, hi); }
+    mark_records_stale(c, lo, hi);
     return NHDFIT_OK;
 }
 

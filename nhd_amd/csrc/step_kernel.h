@@ -1,4 +1,4 @@
-// step_kernel.h - k_step itself (five roles, one launch), its per-role stand-alone form and the node-record kernels.
+// step_kernel.h - k_step itself (five roles, one launch), the single-launch finds and the node-record kernels.
 // Device code of libnhdfit.so; included by nhdfit.hip inside its anonymous namespace, in this order: step_digest.h,
 // step_fit.h, step_map.h, step_kernel.h, seq_kernel.h (one translation unit: the roles are fused into one kernel).
 // gfx950 only.
@@ -28,14 +28,6 @@ __device__ __forceinline__ void stamp(unsigned long long* role_clock, int role, 
         atomicMax(&role_clock[2 * role + 1], (unsigned long long)wall_clock64());
     }
 }
-
-#ifdef NHDFIT_TUNING      // profiling aid of the tuning build (NHDFIT_SPLIT): the fit role as a launch of its own
-template <int BLOCK>
-__global__ __launch_bounds__(BLOCK) void k_fit_only(FitArgs a) {
-    extern __shared__ __align__(16) uint8_t lds[];
-    role_fit<BLOCK>(a, a.busy_from, blockIdx.x, lds);
-}
-#endif
 
 // ---- node records ------------------------------------------------------------------------------------
 // Everything the fit role needs from a node's five planes depends only on the mirror and the dictionary, not on the
@@ -305,26 +297,6 @@ __global__ __launch_bounds__(BLOCK, SPILL ? (BLOCK == 512 ? 4 : 5) : (BLOCK == 5
     extern __shared__ __align__(16) uint8_t lds[];
     step_body<BLOCK, SPILL>(a, a.fit.busy_from, lds);
 }
-
-#ifdef NHDFIT_TUNING
-// Profiling aid of the tuning build (NHDFIT_ROLE_KERNELS=1): one role per launch, so that rocprofv3 --stats names each role's
-// stand-alone time.  Not in libnhdfit.so.
-template <int BLOCK, int ROLE>
-__global__ __launch_bounds__(BLOCK, 6) void k_role(StepArgs a) {
-    extern __shared__ __align__(16) uint8_t lds[];
-    const uint32_t blk = blockIdx.x;
-    if constexpr (ROLE == 0) {
-        if (a.choose_lanes)
-            role_choose_lanes(a.choose, (uint32_t)__builtin_amdgcn_readfirstlane((int)(blk * (BLOCK / 64) + (threadIdx.x >> 6))), (a.shapes_P + kTile - 1) / kTile);
-        else if ((threadIdx.x & 63) == 0)
-            role_choose(a.choose, (uint32_t)__builtin_amdgcn_readfirstlane((int)(blk * (BLOCK / 64) + (threadIdx.x >> 6))),
-                        a.nb_choose * (BLOCK / 64), (a.shapes_P + kTile - 1) / kTile);
-    } else if constexpr (ROLE == 1) role_shapes<BLOCK>(a.shapes_m, a.shapes_h, blk, lds);
-    else if constexpr (ROLE == 2) role_finish<BLOCK>(a.finish_m, a.finish_h, blk, lds);
-    else if constexpr (ROLE == 3) role_digest<BLOCK>(a.digest, blk, lds);
-    else role_fit<BLOCK>(a.fit, a.fit.busy_from, blk, lds);
-}
-#endif
 
 // ---- hand-offs between the blocks of one launch (k_find, k_find1, k_findn) -----------------------------------------------------------------
 // gfx950: a CU's L1 is never refreshed by other CUs' stores, the XCDs' L2s are not coherent with each other.  What a block publishes -

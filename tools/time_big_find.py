@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Cost of the general path for requests (nhdfit_big_find / nhdfit_big_commit: pods with 5..8 processing groups) on BASELINE
 cluster shapes, through ctypes: one big pod per call by group count, a batch of 16 in one call, and a find + commit pair.
-Run under `rocprofv3 --kernel-trace --stats` for k_big_eval / k_big_map / k_big_commit's own durations (tools/r04_big_prof.sh)."""
+Run under `rocprofv3 --kernel-trace --stats` for k_big_eval / k_big_map / k_big_commit's own durations."""
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np

@@ -1,7 +1,6 @@
 #!/usr/bin/env python3
 """Latency of nhdfit_find for ONE pod (the single-launch form) on BASELINE cluster shapes, through ctypes.
-NHDFIT_LIBRARY=.../libnhdfit_tuning.so NHDFIT_ROLE_TIMES=0 prints the phases of a launch on the device clock;
-NHDFIT_FIND_BLOCKS=<n> overrides the number of fit blocks."""
+NHDFIT_LIBRARY=.../libnhdfit_tuning.so NHDFIT_ROLE_TIMES=0 prints the phases of a launch on the device clock."""
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
