@@ -610,6 +610,30 @@ int nhdfit_headroom(nhdfit_ctx* ctx, const nhdfit_req* reqs, uint32_t P, const u
 int nhdfit_group_headroom(nhdfit_group* g, const nhdfit_req* reqs, uint32_t P, const uint64_t* const* cand, uint32_t max_per_node,
                           nhdfit_headroom_sum* sum_out, uint16_t* const* counts_out);
 
+/* ---- headroom limits: the stage that ends each node's run -------------------------------------------------------------
+ * nhdfit_headroom with one more answer per (template, node): which resource ran out.  limit(node, template) is the stage
+ * nhdfit_explain's stage function (NHDFIT_STAGE_*, nhd/Matcher.py:65-391) names for the template on the node IN THE STATE IN
+ * WHICH ITS RUN ENDED - the private copy after the last SetPhysicalIdsFromMapping / ClaimPodNICResources that succeeded
+ * (nhd/Node.py:663-841, :644-646), the mirror's own state where no replica fit - with IsBusy() false (nhd/Matcher.py:104 never
+ * drops a node here: BUSY does not occur) and the candidate / InitialNodeFilter decision of the run (nhd/NHDScheduler.py:235-247).
+ * FITS occurs only on nodes that reached max_per_node with room left: the run stopped there, not the node (a node may also run out
+ * of a resource with the very replica that reaches the bound: it names that resource).  A node flagged
+ * NHDFIT_HEADROOM_STOPPED or NHDFIT_HEADROOM_NOT_EVALUATED has no stage - the reference leaves a half-committed node behind
+ * where it raises (nhd/Node.py:686, :826-841) - its code is NHDFIT_LIMIT_NONE and it is in no histogram bin:
+ *     sum(limits_out[p][*]) + sum_out[p].stopped + sum_out[p].not_evaluated == n   for every template p.
+ * sum_out and counts_out are bit for bit what nhdfit_headroom returns for the same arguments; limits, errors and side effects
+ * (none) are nhdfit_headroom's. */
+#define NHDFIT_LIMIT_NONE 255u
+/* limits_out [P][NHDFIT_STAGES]: nodes of the mirror per template and stage.  stage_out: NULL, or [P][n] stage codes (or
+ * NHDFIT_LIMIT_NONE) by node index.  The final states take 208 bytes per (template, node): the templates are worked off in slabs
+ * of a fixed budget of device memory (64 MiB; one template where a single one needs more); the answers do not depend on it. */
+int nhdfit_headroom_limits(nhdfit_ctx* ctx, const nhdfit_req* reqs, uint32_t P, const uint64_t* cand, uint32_t max_per_node,
+                           nhdfit_headroom_sum* sum_out, uint16_t* counts_out, uint32_t* limits_out, uint8_t* stage_out);
+/* ... over every shard of a group: sum_out as nhdfit_group_headroom, limits_out summed over the devices; counts_out / stage_out
+ * NULL, or one [P][shard's n] buffer (or NULL) per shard.  cand as nhdfit_group_find. */
+int nhdfit_group_headroom_limits(nhdfit_group* g, const nhdfit_req* reqs, uint32_t P, const uint64_t* const* cand, uint32_t max_per_node,
+                                 nhdfit_headroom_sum* sum_out, uint16_t* const* counts_out, uint32_t* limits_out, uint8_t* const* stage_out);
+
 /* ---- request digest straight from the wire format (host code, no GPU needed) -------------------------
  * The pod's Triad libconfig text -> nhdfit_req, replacing TriadCfgParser(text, False).CfgToTopology(False)
  * (nhd/TriadCfgParser.py:337-380, called from nhd/NHDScheduler.py:262-270) followed by the getters FindNode

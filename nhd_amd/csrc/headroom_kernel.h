@@ -19,7 +19,8 @@
 //     record go into the wavefront's own LDS slice (464 bytes with the placement record the commit writes), then
 //     lone_nic_bits -> map_on_state_wave -> commit_node_wave on the LDS copy -> node_index / lone_pod_fits on the new state, until
 //     it no longer fits, the cap is reached, or the commit reports kCommitWouldRaise / kCommitNewSig (stop, flag, do not count).
-//     Nothing is written back.
+//     Nothing is written back.  Where the caller asks for it (HeadroomArgs::final, nhdfit_headroom_limits) the copy a run of at
+//     least one replica ended in is stored - planes 0-4 and the detail record, 208 bytes - for k_limit_stage (limit_kernel.h).
 //   Results: wavefront 0 stores the chunk's 64 entries as one coalesced 128-byte row of uint16 and adds the chunk to the block's
 //   partial sums in LDS; at the end one atomic per (block, template, field) into the summary record.
 // Every loop has a bound known before it starts: the chunk count (tickets), 64 (set bits), max_per_node (replicas).  No spin wait,
@@ -65,6 +66,8 @@ __device__ __forceinline__ uint32_t headroom_run_wave(NodeState& st, nhdfit_deta
 }
 
 // ---- the launch -------------------------------------------------------------------------------------------------------------------
+struct HeadroomFinal { NodeState st; nhdfit_detail dd; };   // a node's private copy as its run left it (nhdfit_headroom_limits)
+static_assert(sizeof(HeadroomFinal) == 208 && sizeof(HeadroomFinal) % 16 == 0, "planes 0-4 and the detail record, thirteen 16-byte stores");
 struct HeadroomSum { unsigned long long replicas; uint32_t nodes_with_room, max_on_one_node, saturated, stopped, not_evaluated, form; };
 static_assert(sizeof(HeadroomSum) == sizeof(nhdfit_headroom_sum) && sizeof(HeadroomSum) == 32, "the summary record of include/nhdfit.h");
 
@@ -81,6 +84,7 @@ struct HeadroomArgs {
     uint32_t* tickets;                               // [templates], zeroed by the caller
     uint16_t* counts;                                // [templates][chunks * 64]
     HeadroomSum* sum;                                // [templates], zeroed by the caller
+    HeadroomFinal* final;                            // optional [templates][chunks * 64]: the state each run of >= 1 replica ended in (limit_kernel.h)
 };
 constexpr uint32_t kHeadroomBlock = 256, kHeadroomWaves = kHeadroomBlock / 64;
 constexpr size_t kHeadroomLds = kLoneLds + lds_slice(kHeadroomWaves * sizeof(NodeState)) + lds_slice(kHeadroomWaves * sizeof(nhdfit_detail)) +
@@ -160,6 +164,16 @@ __global__ __launch_bounds__(kHeadroomBlock) void k_headroom(HeadroomArgs a) {
             __builtin_amdgcn_wave_barrier();
             const uint32_t e = headroom_run_wave<G4>(st, dd, pl, r, x, lane);
             if (lane == 0u) s_cnt[b] = e;
+            if (a.final && (e & NHDFIT_HEADROOM_COUNT_MASK)) {           // (block-uniform pointer, wavefront-uniform entry) the copy as the last commit
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // left it, by the lanes that loaded it: thirteen 16-byte stores
+                __builtin_amdgcn_wave_barrier();
+                uint4* f = reinterpret_cast<uint4*>(a.final + ((size_t)tpl * a.chunks * 64u + v));
+                if (lane < 5u) f[lane] = uint4{sw[lane * 4 + 0], sw[lane * 4 + 1], sw[lane * 4 + 2], sw[lane * 4 + 3]};
+                if (lane >= 8u && lane < 8u + sizeof(nhdfit_detail) / 16) {
+                    const uint32_t* dw = reinterpret_cast<const uint32_t*>(&dd) + (lane - 8u) * 4u;
+                    f[5u + lane - 8u] = uint4{dw[0], dw[1], dw[2], dw[3]};
+                }
+            }
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
             __builtin_amdgcn_wave_barrier();                             // (the slice is the next node's)
         }

@@ -65,6 +65,7 @@ namespace {
 #include "big_kernel.h"
 #include "explain_kernel.h"
 #include "headroom_kernel.h"
+#include "limit_kernel.h"
 
 // ------------------------------------------------------------------------------------------------
 // host side
@@ -276,6 +277,8 @@ struct nhdfit_ctx {
     DevBuf<uint32_t> ex_counts, ex_flags; DevBuf<uint64_t> ex_cand; DevBuf<uint8_t> ex_stage;
     // nhdfit_headroom (headroom_kernel.h): buffers of its own as well
     DevBuf<nhdfit_req> hr_reqs; DevBuf<uint32_t> hr_tickets; DevBuf<HeadroomSum> hr_sum; DevBuf<uint16_t> hr_counts; DevBuf<uint64_t> hr_cand;
+    // nhdfit_headroom_limits (limit_kernel.h): the runs' final states, a slab of templates at a time, and the stage histogram / matrix
+    DevBuf<HeadroomFinal> hr_final; DevBuf<uint32_t> hr_hist; DevBuf<uint8_t> hr_stage;
     int wide_slot(uint32_t node) const {
         auto it = std::lower_bound(wide_index.begin(), wide_index.end(), node);
         return it != wide_index.end() && *it == node ? (int)(it - wide_index.begin()) : -1;
@@ -2926,9 +2929,12 @@ int nhdfit_group_explain(nhdfit_group* g, const nhdfit_req* reqs, uint32_t P, do
 }
 
 // ---- headroom: how many more replicas of a pod template each node can take (headroom_kernel.h) ---------------------------------------
-int nhdfit_headroom(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, const uint64_t* cand, uint32_t max_per_node, nhdfit_headroom_sum* sum_out,
-                    uint16_t* counts_out) {
-    if (!c) return NHDFIT_E_INVAL;
+}  // extern "C"
+namespace {
+// nhdfit_headroom (limits_out == nullptr: one launch over every template, nothing kept) and nhdfit_headroom_limits (the templates in
+// slabs of `slab_bytes` of final states; per slab k_headroom with HeadroomArgs::final, then k_limit_stage on what it left)
+int headroom_run(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, const uint64_t* cand, uint32_t max_per_node, nhdfit_headroom_sum* sum_out,
+                 uint16_t* counts_out, uint32_t* limits_out, uint8_t* stage_out, size_t slab_bytes) {
     if (!reqs || !P || !sum_out) return fail(c, NHDFIT_E_INVAL, "headroom: requests and sum_out are required");
     if (!max_per_node || max_per_node > NHDFIT_HEADROOM_COUNT_MASK)
         return fail(c, NHDFIT_E_INVAL, "headroom: max_per_node is %u (1 .. %u)", max_per_node, (unsigned)NHDFIT_HEADROOM_COUNT_MASK);
@@ -2936,6 +2942,7 @@ int nhdfit_headroom(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, const uin
     for (uint32_t p = 0; p < P; ++p)
         if (reqs[p].hugepages_gb > kMaxHpRows - 2) return fail(c, NHDFIT_E_LIMIT, "template %u asks for %d GB of hugepages (<= %d)", p, reqs[p].hugepages_gb, kMaxHpRows - 2);
     memset(sum_out, 0, (size_t)P * sizeof *sum_out);
+    if (limits_out) memset(limits_out, 0, (size_t)P * NHDFIT_STAGES * sizeof(uint32_t));
     const uint32_t n = c->n;
     if (!n) return NHDFIT_OK;
     if (!c->ncls || !c->nsig) return fail(c, NHDFIT_E_STATE, "set the dictionary first (nhdfit_set_dictionary)");
@@ -2950,6 +2957,14 @@ int nhdfit_headroom(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, const uin
     HIPCHK(c, c->hr_tickets.reserve(P));
     HIPCHK(c, c->hr_sum.reserve(P));
     HIPCHK(c, c->hr_counts.reserve((size_t)P * pitch));
+    // the final states of one slab of templates: as many as the budget holds, one at the least (every loop below is bounded by P)
+    const uint32_t slab = limits_out ? (uint32_t)std::min<size_t>(P, std::max<size_t>(1, slab_bytes / (pitch * sizeof(HeadroomFinal)))) : P;
+    if (limits_out) {
+        HIPCHK(c, c->hr_final.reserve((size_t)slab * pitch));
+        HIPCHK(c, c->hr_hist.reserve((size_t)P * NHDFIT_STAGES));
+        if (stage_out) HIPCHK(c, c->hr_stage.reserve((size_t)P * n));
+        HIPCHK(c, hipMemsetAsync(c->hr_hist.p, 0, (size_t)P * NHDFIT_STAGES * sizeof(uint32_t), c->streams.use(0)));
+    }
     HIPCHK(c, hipMemcpyAsync(c->hr_reqs.p, reqs, (size_t)P * sizeof *reqs, hipMemcpyHostToDevice, c->streams.use(0)));
     HIPCHK(c, hipMemsetAsync(c->hr_tickets.p, 0, (size_t)P * sizeof(uint32_t), c->streams.use(0)));
     HIPCHK(c, hipMemsetAsync(c->hr_sum.p, 0, (size_t)P * sizeof(HeadroomSum), c->streams.use(0)));
@@ -2971,20 +2986,37 @@ int nhdfit_headroom(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, const uin
     a.chunks = chunks; a.cap = max_per_node;
     a.tickets = c->hr_tickets.p; a.counts = c->hr_counts.p; a.sum = c->hr_sum.p;
     a.all_generic = a.mt.choose_tab && a.mt.st.info ? 0u : 1u;
-    bool any_wave = false, any_g4 = false;
     std::vector<uint32_t> form(P);
-    for (uint32_t p = 0; p < P; ++p) {
-        const bool g4 = a.all_generic || (req_valid(reqs[p]) && reqs[p].n_groups > 3);
-        form[p] = g4 ? NHDFIT_HEADROOM_FORM_GENERIC : NHDFIT_HEADROOM_FORM_WAVE;
-        (g4 ? any_g4 : any_wave) = true;
-    }
-    // blocks per template: the chip's block slots shared out among the templates, a chunk per block at the least
+    for (uint32_t p = 0; p < P; ++p)
+        form[p] = a.all_generic || (req_valid(reqs[p]) && reqs[p].n_groups > 3) ? NHDFIT_HEADROOM_FORM_GENERIC : NHDFIT_HEADROOM_FORM_WAVE;
     const uint32_t slots = 4u * (uint32_t)c->prop.multiProcessorCount;
-    const uint32_t nb = std::max(1u, std::min(chunks, (slots + P - 1) / P));
-    if (any_wave) hipLaunchKernelGGL(k_headroom<false>, dim3(nb, P), dim3(kHeadroomBlock), kHeadroomLds, c->streams.use(0), a);
-    HIPCHK(c, hipGetLastError());
-    if (any_g4) hipLaunchKernelGGL(k_headroom<true>, dim3(nb, P), dim3(kHeadroomBlock), kHeadroomLds, c->streams.use(0), a);
-    HIPCHK(c, hipGetLastError());
+    for (uint32_t t0 = 0; t0 < P; t0 += slab) {                          // (plain headroom: one turn)
+        const uint32_t S = std::min(slab, P - t0);
+        bool any_wave = false, any_g4 = false;
+        for (uint32_t p = t0; p < t0 + S; ++p) (form[p] == NHDFIT_HEADROOM_FORM_GENERIC ? any_g4 : any_wave) = true;
+        // the kernel indexes by blockIdx.y: it is handed the slab's rows; only `final` is the slab's own
+        a.reqs = c->hr_reqs.p + t0; a.tickets = c->hr_tickets.p + t0; a.sum = c->hr_sum.p + t0; a.counts = c->hr_counts.p + (size_t)t0 * pitch;
+        a.final = limits_out ? c->hr_final.p : nullptr;
+        // blocks per template: the chip's block slots shared out among the templates, a chunk per block at the least
+        const uint32_t nb = std::max(1u, std::min(chunks, (slots + S - 1) / S));
+        if (any_wave) hipLaunchKernelGGL(k_headroom<false>, dim3(nb, S), dim3(kHeadroomBlock), kHeadroomLds, c->streams.use(0), a);
+        HIPCHK(c, hipGetLastError());
+        if (any_g4) hipLaunchKernelGGL(k_headroom<true>, dim3(nb, S), dim3(kHeadroomBlock), kHeadroomLds, c->streams.use(0), a);
+        HIPCHK(c, hipGetLastError());
+        if (!limits_out) continue;
+        LimitArgs la;
+        memset(&la, 0, sizeof la);
+        la.p0 = a.p0; la.p1 = a.p1; la.p2 = a.p2; la.p3 = a.p3; la.p4 = a.p4; la.det = a.det; la.n = n;
+        la.reqs = c->hr_reqs.p; la.caps = c->caps.p; la.cand = a.cand;
+        la.counts = c->hr_counts.p; la.pitch = pitch; la.final = c->hr_final.p; la.tpl0 = t0;
+        la.hist = c->hr_hist.p; la.stage = stage_out ? c->hr_stage.p : nullptr;
+        hipLaunchKernelGGL(k_limit_stage, dim3((n + kLimitThreads - 1) / kLimitThreads, S), dim3(kLimitThreads), 0, c->streams.use(0), la);
+        HIPCHK(c, hipGetLastError());
+    }
+    if (limits_out) {
+        HIPCHK(c, hipMemcpyAsync(limits_out, c->hr_hist.p, (size_t)P * NHDFIT_STAGES * sizeof(uint32_t), hipMemcpyDeviceToHost, c->streams.use(0)));
+        if (stage_out) HIPCHK(c, hipMemcpyAsync(stage_out, c->hr_stage.p, (size_t)P * n, hipMemcpyDeviceToHost, c->streams.use(0)));
+    }
     static_assert(sizeof(HeadroomSum) == sizeof(nhdfit_headroom_sum), "copied out as it is");
     HIPCHK(c, hipMemcpyAsync(sum_out, c->hr_sum.p, (size_t)P * sizeof *sum_out, hipMemcpyDeviceToHost, c->streams.use(0)));
     if (counts_out)
@@ -2994,6 +3026,46 @@ int nhdfit_headroom(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, const uin
     for (uint32_t p = 0; p < P; ++p) sum_out[p].form = form[p];
     return NHDFIT_OK;
 }
+}  // namespace
+extern "C" {
+
+int nhdfit_headroom(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, const uint64_t* cand, uint32_t max_per_node, nhdfit_headroom_sum* sum_out,
+                    uint16_t* counts_out) {
+    if (!c) return NHDFIT_E_INVAL;
+    return headroom_run(c, reqs, P, cand, max_per_node, sum_out, counts_out, nullptr, nullptr, 0);
+}
+
+int nhdfit_headroom_limits(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, const uint64_t* cand, uint32_t max_per_node, nhdfit_headroom_sum* sum_out,
+                           uint16_t* counts_out, uint32_t* limits_out, uint8_t* stage_out) {
+    if (!c) return NHDFIT_E_INVAL;
+    if (!limits_out) return fail(c, NHDFIT_E_INVAL, "headroom limits: limits_out is required");
+    return headroom_run(c, reqs, P, cand, max_per_node, sum_out, counts_out, limits_out, stage_out, kHeadroomSlabBytes);
+}
+
+// Not part of include/nhdfit.h: nhdfit_headroom_limits with the budget of final states as an argument (0: the default), so that a test
+// can make a few templates take several slabs.  The answers do not depend on it.
+int nhdfit_headroom_limits_slab(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, const uint64_t* cand, uint32_t max_per_node, nhdfit_headroom_sum* sum_out,
+                                uint16_t* counts_out, uint32_t* limits_out, uint8_t* stage_out, uint64_t slab_bytes) {
+    if (!c) return NHDFIT_E_INVAL;
+    if (!limits_out) return fail(c, NHDFIT_E_INVAL, "headroom limits: limits_out is required");
+    return headroom_run(c, reqs, P, cand, max_per_node, sum_out, counts_out, limits_out, stage_out, slab_bytes ? (size_t)slab_bytes : kHeadroomSlabBytes);
+}
+
+}  // extern "C"
+namespace {
+// a shard's summary records into the group's (nhdfit_group_headroom, nhdfit_group_headroom_limits)
+void add_headroom_sums(nhdfit_headroom_sum* sum_out, const nhdfit_headroom_sum* part, uint32_t P) {
+    for (uint32_t p = 0; p < P; ++p) {
+        nhdfit_headroom_sum& s = sum_out[p];
+        s.replicas += part[p].replicas; s.nodes_with_room += part[p].nodes_with_room; s.saturated += part[p].saturated;
+        s.stopped += part[p].stopped; s.not_evaluated += part[p].not_evaluated;
+        s.max_on_one_node = std::max(s.max_on_one_node, part[p].max_on_one_node);
+        s.form = std::max(s.form, part[p].form);
+    }
+}
+}  // namespace
+
+extern "C" {
 
 int nhdfit_group_headroom(nhdfit_group* g, const nhdfit_req* reqs, uint32_t P, const uint64_t* const* cand, uint32_t max_per_node,
                           nhdfit_headroom_sum* sum_out, uint16_t* const* counts_out) {
@@ -3004,13 +3076,25 @@ int nhdfit_group_headroom(nhdfit_group* g, const nhdfit_req* reqs, uint32_t P, c
         nhdfit_ctx* c = g->ctx[k];
         const int rc = nhdfit_headroom(c, reqs, P, cand ? cand[k] : nullptr, max_per_node, part.data(), counts_out ? counts_out[k] : nullptr);
         if (rc) { g->err = c->err; return rc; }
-        for (uint32_t p = 0; p < P; ++p) {
-            nhdfit_headroom_sum& s = sum_out[p];
-            s.replicas += part[p].replicas; s.nodes_with_room += part[p].nodes_with_room; s.saturated += part[p].saturated;
-            s.stopped += part[p].stopped; s.not_evaluated += part[p].not_evaluated;
-            s.max_on_one_node = std::max(s.max_on_one_node, part[p].max_on_one_node);
-            s.form = std::max(s.form, part[p].form);
-        }
+        add_headroom_sums(sum_out, part.data(), P);
+    }
+    return NHDFIT_OK;
+}
+
+int nhdfit_group_headroom_limits(nhdfit_group* g, const nhdfit_req* reqs, uint32_t P, const uint64_t* const* cand, uint32_t max_per_node,
+                                 nhdfit_headroom_sum* sum_out, uint16_t* const* counts_out, uint32_t* limits_out, uint8_t* const* stage_out) {
+    if (!g || !reqs || !P || !sum_out || !limits_out) return NHDFIT_E_INVAL;
+    std::vector<nhdfit_headroom_sum> part(P);
+    std::vector<uint32_t> hist((size_t)P * NHDFIT_STAGES);
+    memset(sum_out, 0, (size_t)P * sizeof *sum_out);
+    memset(limits_out, 0, hist.size() * sizeof(uint32_t));
+    for (size_t k = 0; k < g->ctx.size(); ++k) {
+        nhdfit_ctx* c = g->ctx[k];
+        const int rc = nhdfit_headroom_limits(c, reqs, P, cand ? cand[k] : nullptr, max_per_node, part.data(), counts_out ? counts_out[k] : nullptr,
+                                              hist.data(), stage_out ? stage_out[k] : nullptr);
+        if (rc) { g->err = c->err; return rc; }
+        add_headroom_sums(sum_out, part.data(), P);
+        for (size_t j = 0; j < hist.size(); ++j) limits_out[j] += hist[j];
     }
     return NHDFIT_OK;
 }

@@ -322,6 +322,31 @@ class Engine:
             self._chk(self.lib.nhdfit_headroom(self.ctx, _p(reqs), P, _p(cand), int(max_per_node), _p(sums), _p(counts)))
         return sums, counts
 
+    def headroom_limits(self, reqs: np.ndarray, cand: Optional[np.ndarray] = None, max_per_node: int = 512, per_node: bool = False,
+                        _slab_bytes: Optional[int] = None):
+        """(sums, entries or None, limits [P][STAGES] uint32, stages [P][n] uint8 or None): headroom() - the same sums and entries -
+        and the stage that ended each node's run (nhdfit_headroom_limits): per template the nodes per stage, and per node the stage
+        code or pack.LIMIT_NONE where the entry is flagged.  `_slab_bytes`: the device-memory budget of the runs' final states (tests:
+        a small one makes the call take several slabs of templates)."""
+        reqs = np.ascontiguousarray(reqs, dtype=pack.REQ)
+        P = len(reqs)
+        sums = np.zeros(P, pack.HEADROOM_SUM)
+        counts = np.zeros((P, self.n), np.uint16) if per_node else None
+        limits = np.zeros((P, STAGES), np.uint32)
+        stages = np.zeros((P, self.n), np.uint8) if per_node else None
+        if cand is not None:
+            cand = np.ascontiguousarray(cand, dtype=np.uint64)
+            assert cand.shape == ((self.n + 63) // 64,)
+        if P:
+            args = (self.ctx, _p(reqs), P, _p(cand), int(max_per_node), _p(sums), _p(counts), _p(limits), _p(stages))
+            if _slab_bytes is None:
+                self._chk(self.lib.nhdfit_headroom_limits(*args))
+            else:                                                   # the library's entry outside include/nhdfit.h that takes the budget
+                fn = self.lib.nhdfit_headroom_limits_slab
+                fn.restype, fn.argtypes = ctypes.c_int, _lib._SIGS["nhdfit_headroom_limits"][1] + [ctypes.c_uint64]
+                self._chk(fn(*args, int(_slab_bytes)))
+        return sums, counts, limits, stages
+
     def big_commit(self, node: int, req: np.ndarray, mapping: np.ndarray, busy_time: float) -> np.ndarray:
         """The commit step of a big request on node `node` (ordinary or wide): updates the mirror, returns pack.BIG_PLACEMENT."""
         out = np.zeros((), pack.BIG_PLACEMENT)
@@ -751,10 +776,7 @@ class GroupEngine:
                 lo, hi = self._bounds[k]
                 if hi > lo:
                     sm, ct = s.headroom(reqs, cand=masks[k], max_per_node=max_per_node, per_node=per_node)
-                    for f in ("replicas", "nodes_with_room", "saturated", "stopped", "not_evaluated"):
-                        sums[f] += sm[f]
-                    sums["max_on_one_node"] = np.maximum(sums["max_on_one_node"], sm["max_on_one_node"])
-                    sums["form"] = np.maximum(sums["form"], sm["form"])
+                    _add_headroom_sums(sums, sm)
                     parts.append(ct)
                 else:
                     parts.append(None)
@@ -763,6 +785,50 @@ class GroupEngine:
                 if ct is not None:
                     counts[:, lo:hi] = ct
         return sums, counts
+
+    def headroom_limits(self, reqs: np.ndarray, cand: Optional[np.ndarray] = None, max_per_node: int = 512, per_node: bool = False):
+        """Engine.headroom_limits over every shard: sums and histograms added over the devices (nhdfit_group_headroom_limits), entries
+        and stages put together in global node order."""
+        reqs = np.ascontiguousarray(reqs, dtype=pack.REQ)
+        P = len(reqs)
+        sums = np.zeros(P, pack.HEADROOM_SUM)
+        counts = np.zeros((P, self.n), np.uint16) if per_node else None
+        limits = np.zeros((P, STAGES), np.uint32)
+        stages = np.zeros((P, self.n), np.uint8) if per_node else None
+        if cand is not None:
+            cand = np.ascontiguousarray(cand, dtype=np.uint64)
+        masks = [None if cand is None else np.ascontiguousarray(cand[lo // 64:(hi + 63) // 64]) for lo, hi in self._bounds]
+        if not P:
+            return sums, counts, limits, stages
+        if self.group is not None:
+            parts = [np.zeros((P, hi - lo), np.uint16) if per_node and hi > lo else None for lo, hi in self._bounds]
+            sparts = [np.zeros((P, hi - lo), np.uint8) if per_node and hi > lo else None for lo, hi in self._bounds]
+            cptr = (ctypes.c_void_p * len(self.shards))(*[None if m is None else m.ctypes.data for m in masks])
+            kptr = (ctypes.c_void_p * len(self.shards))(*[None if x is None else x.ctypes.data for x in parts])
+            sptr = (ctypes.c_void_p * len(self.shards))(*[None if x is None else x.ctypes.data for x in sparts])
+            rc = self.lib.nhdfit_group_headroom_limits(self.group, _p(reqs), P, cptr if cand is not None else None, int(max_per_node), _p(sums),
+                                                       kptr if per_node else None, _p(limits), sptr if per_node else None)
+            if rc != 0:
+                raise _lib.NhdFitError(rc, (self.lib.nhdfit_group_last_error(self.group) or b"?").decode())
+        else:
+            parts, sparts = [], []
+            for k, s in enumerate(self.shards):
+                lo, hi = self._bounds[k]
+                if hi > lo:
+                    sm, ct, lm, st = s.headroom_limits(reqs, cand=masks[k], max_per_node=max_per_node, per_node=per_node)
+                    _add_headroom_sums(sums, sm)
+                    limits += lm
+                    parts.append(ct)
+                    sparts.append(st)
+                else:
+                    parts.append(None)
+                    sparts.append(None)
+        if per_node:
+            for (lo, hi), ct, st in zip(self._bounds, parts, sparts):
+                if ct is not None:
+                    counts[:, lo:hi] = ct
+                    stages[:, lo:hi] = st
+        return sums, counts, limits, stages
 
     def big_commit(self, node: int, req, mapping, busy_time):
         k = self._shard_of(node)
@@ -809,6 +875,14 @@ class GroupEngine:
 
     def stats(self):
         return self.shards[0].stats()
+
+
+def _add_headroom_sums(sums: np.ndarray, part: np.ndarray) -> None:
+    """A shard's pack.HEADROOM_SUM records into the group's (what nhdfit_group_headroom does with them)."""
+    for f in ("replicas", "nodes_with_room", "saturated", "stopped", "not_evaluated"):
+        sums[f] += part[f]
+    sums["max_on_one_node"] = np.maximum(sums["max_on_one_node"], part["max_on_one_node"])
+    sums["form"] = np.maximum(sums["form"], part["form"])
 
 
 def winner_index(score: int) -> int:

@@ -166,11 +166,19 @@ class Headroom:
     succeeded before it), `not_evaluated` (wide nodes, ENABLE_SHARING mirrors: no figure), `unmirrored` (nodes of `nl` the device
     does not hold: they never match) and, when asked for, `per_node` (uint16 counts in `nl` order) with `flags` (the STOPPED /
     NOT_EVALUATED bits of include/nhdfit.h beside them).  `form`: which kernel instantiation answered (pack.HEADROOM_FORM_*).
-    `error`: why the template itself could not be evaluated - then nothing is a number: every node counts as not evaluated."""
+    `error`: why the template itself could not be evaluated - then nothing is a number: every node counts as not evaluated.
+    Asked for with limits=True: `limits` (stage name -> nodes of `nl` whose run ended at that stage - the resource that ran out
+    first; "FITS" occurs only on nodes that reached `max_per_node` with room left - a node may also run out of a resource with the
+    very replica that reaches the bound; stopped, not evaluated and unmirrored nodes are charged to no stage) and, with
+    per_node=True, `limit_stages` (uint8 per node in `nl` order: the stage code, or 255 = pack.LIMIT_NONE = UNMIRRORED for a
+    node without one - `flags` tells a stopped or not evaluated node, whose flag is set, from an unmirrored one).  Both are None
+    otherwise."""
 
     def __init__(self, nodes: int, names: Optional[List[str]] = None, replicas: int = 0, nodes_with_room: int = 0, max_on_one_node: int = 0,
                  saturated: int = 0, stopped: int = 0, not_evaluated: int = 0, unmirrored: int = 0, form: int = 0, max_per_node: int = 0,
-                 per_node: Optional[np.ndarray] = None, flags: Optional[np.ndarray] = None, error: Optional[str] = None):
+                 per_node: Optional[np.ndarray] = None, flags: Optional[np.ndarray] = None, error: Optional[str] = None,
+                 limits: Optional[Dict[str, int]] = None, limit_stages: Optional[np.ndarray] = None):
+        self.limits, self.limit_stages = limits, limit_stages
         self.nodes, self._names = nodes, names
         self.replicas, self.nodes_with_room, self.max_on_one_node = int(replicas), int(nodes_with_room), int(max_on_one_node)
         self.saturated, self.stopped, self.not_evaluated, self.unmirrored = int(saturated), int(stopped), int(not_evaluated), int(unmirrored)
@@ -198,6 +206,20 @@ class Headroom:
         if self.unmirrored:
             notes.append(f"{_spaced(self.unmirrored)} not mirrored on the device")
         return text + ("; " + ", ".join(notes) if notes else "")
+
+    def limit_summary(self) -> str:
+        """"further replicas are held back by: short of CPU cores on 40 210 nodes, short of NIC bandwidth on 12 001, ..." (limits=True
+        calls only), the stages ordered by the nodes they hold."""
+        if self.limits is None:
+            raise ValueError("limit_summary() needs the limits: ask for limits=True")
+        if self.error is not None:
+            return f"the pod was not evaluated against the {_spaced(self.nodes)} nodes: {self.error}."
+        held = sorted(((k, s) for s, k in self.limits.items() if k and s != "FITS"), key=lambda x: -x[0])
+        parts = [f"{_STAGE_TEXT[s]} on {_spaced(k)}" + (" nodes" if i == 0 else "") for i, (k, s) in enumerate(held)]
+        text = "further replicas are held back by: " + ", ".join(parts) if parts else "nothing holds further replicas back"
+        if self.limits.get("FITS"):
+            text += f"; {_spaced(self.limits['FITS'])} nodes reached the limit of {_spaced(self.max_per_node)} per node with room left"
+        return text
 
     def __repr__(self) -> str:
         return f"Headroom({self.summary()!r})"
@@ -821,13 +843,13 @@ class HipMatcher:
         return out
 
     def Headroom(self, nl: Dict[str, object], top, pod_groups: Optional[Sequence[str]] = None, per_node: bool = False,
-                 max_per_node: int = 512, strict: Optional[bool] = None) -> Headroom:
+                 max_per_node: int = 512, strict: Optional[bool] = None, limits: bool = False) -> Headroom:
         """HeadroomMany for one pod template."""
         return self.HeadroomMany(nl, [top], None if pod_groups is None else [pod_groups], per_node=per_node, max_per_node=max_per_node,
-                                 strict=strict)[0]
+                                 strict=strict, limits=limits)[0]
 
     def HeadroomMany(self, nl: Dict[str, object], tops: Sequence[object], pod_groups: Optional[Sequence[Sequence[str]]] = None,
-                     per_node: bool = False, max_per_node: int = 512, strict: Optional[bool] = None) -> List[Headroom]:
+                     per_node: bool = False, max_per_node: int = 512, strict: Optional[bool] = None, limits: bool = False) -> List[Headroom]:
         """How many more replicas of each pod template of `tops` the nodes of `nl` can take, counted on the device (nhdfit_headroom):
         per node the number of times FindNode -> SetPhysicalIdsFromMapping -> ClaimPodNICResources succeeds back to back on a private
         copy of the node, busy windows out of the way (capacity, not rate: there is no `now`).  The mirror state is the one
@@ -835,7 +857,10 @@ class HipMatcher:
         `max_per_node` (1..16383) bounds a node's run - a template that asks for nothing would fit for ever.  Wide nodes and
         ENABLE_SHARING mirrors are reported as not evaluated, never as a number.  A template no request record can express (5..8
         processing groups, hugepages beyond the pod tile, an unsupported request) or a device error comes back with `error` set
-        and everything not evaluated - `strict=True` (default: the matcher's) raises instead."""
+        and everything not evaluated - `strict=True` (default: the matcher's) raises instead.
+        limits=True (nhdfit_headroom_limits): the same figures and, per template, the stage that ended each node's run - the stage
+        ExplainNode would name for the template on the node in the state its last replica left it, nothing busy (Headroom.limits,
+        Headroom.limit_stages, Headroom.limit_summary())."""
         strict = self.strict if strict is None else strict
         n_pods = len(tops)
         if n_pods == 0:
@@ -845,7 +870,8 @@ class HipMatcher:
         names = list(nl)
         if len(nl) == 0:
             return [Headroom(0, names, max_per_node=max_per_node, per_node=np.zeros(0, np.uint16) if per_node else None,
-                             flags=np.zeros(0, np.uint16) if per_node else None) for _ in range(n_pods)]
+                             flags=np.zeros(0, np.uint16) if per_node else None, limits={s: 0 for s in STAGES} if limits else None,
+                             limit_stages=np.zeros(0, np.uint8) if limits and per_node else None) for _ in range(n_pods)]
         errors: Dict[int, str] = {}
         for p, top in enumerate(tops):
             if len(top.proc_groups) == 0:
@@ -857,7 +883,7 @@ class HipMatcher:
         cand = self._sync_mirror(nl)
         n_unmirrored = sum(1 for nm in nl if nm in self.packer.unmirrored)
         idx = [p for p in range(n_pods) if p not in errors]
-        sums, counts = None, None
+        sums, counts, hist, stages = None, None, None, None
         if idx:
             beyond: List[Tuple[int, str]] = []
             reqs = self.packer.digest_many([tops[p] for p in idx], None if pod_groups is None else [pod_groups[p] for p in idx], unsupported=beyond)
@@ -868,7 +894,22 @@ class HipMatcher:
             try:
                 self.packer.close_signatures()             # every NIC state a commit can produce has a signature
                 self.engine.set_dictionary(self.packer)
-                sums, counts = self.engine.headroom(reqs, cand=cand, max_per_node=int(max_per_node), per_node=per_node)
+                if limits:
+                    # nodes the device does not hold are left out of the call, as ExplainNodes leaves them out (their placeholders would
+                    # be charged to a stage; their count is 0 either way) and reported on their own
+                    off = [self._index[nm] for nm in self.packer.unmirrored if nm in self._index]
+                    if off:
+                        n = len(self._names)
+                        bits = np.zeros(((n + 63) // 64) * 64, dtype=bool)
+                        if cand is None:
+                            bits[:n] = True
+                        else:
+                            bits[:] = np.unpackbits(cand.view(np.uint8), bitorder="little").astype(bool)
+                        bits[off] = False
+                        cand = np.ascontiguousarray(np.packbits(bits.reshape(-1, 64), axis=1, bitorder="little").view("<u8").reshape(-1))
+                    sums, counts, hist, stages = self.engine.headroom_limits(reqs, cand=cand, max_per_node=int(max_per_node), per_node=per_node)
+                else:
+                    sums, counts = self.engine.headroom(reqs, cand=cand, max_per_node=int(max_per_node), per_node=per_node)
             except NhdFitError as e:
                 if strict:
                     raise
@@ -877,19 +918,33 @@ class HipMatcher:
         for p in sorted(errors):
             self.logger.error("headroom: pod %d of the call is not evaluated: %s", p, errors[p])
         order = np.fromiter((self._index[nm] for nm in nl), dtype=np.int64, count=len(nl)) if per_node else None
+        outside = 0
+        if limits and hist is not None:
+            # the device charges NOT_CANDIDATE to every node of the mirror outside `cand`: nodes that are not in `nl`, and the unmirrored ones
+            n = len(self._names)
+            outside = 0 if cand is None else n - int(np.unpackbits(cand.view(np.uint8), bitorder="little")[:n].sum())
+            off = [self._index[nm] for nm in self.packer.unmirrored if nm in self._index]
+            if per_node and off:
+                stages[:, off] = UNMIRRORED
         out = []
         for p in range(n_pods):
             if p in errors:
-                out.append(Headroom(len(nl), names, not_evaluated=len(nl), unmirrored=n_unmirrored, max_per_node=max_per_node, error=errors[p]))
+                out.append(Headroom(len(nl), names, not_evaluated=len(nl), unmirrored=n_unmirrored, max_per_node=max_per_node, error=errors[p],
+                                    limits={s: 0 for s in STAGES} if limits else None))
                 continue
             k = idx.index(p)
             sm = sums[k]
             e = counts[k][order] if per_node else None
+            lim = None
+            if limits:
+                lim = {s: int(hist[k, j]) for j, s in enumerate(STAGES)}
+                lim["NOT_CANDIDATE"] -= outside
             out.append(Headroom(len(nl), names, replicas=sm["replicas"], nodes_with_room=sm["nodes_with_room"], max_on_one_node=sm["max_on_one_node"],
                                 saturated=sm["saturated"], stopped=sm["stopped"], not_evaluated=sm["not_evaluated"], unmirrored=n_unmirrored,
                                 form=sm["form"], max_per_node=max_per_node,
                                 per_node=None if e is None else (e & np.uint16(pack.HEADROOM_COUNT_MASK)),
-                                flags=None if e is None else (e & np.uint16(pack.HEADROOM_STOPPED | pack.HEADROOM_NOT_EVALUATED))))
+                                flags=None if e is None else (e & np.uint16(pack.HEADROOM_STOPPED | pack.HEADROOM_NOT_EVALUATED)),
+                                limits=lim, limit_stages=stages[k][order] if limits and per_node else None))
         return out
 
     @property

@@ -6,10 +6,13 @@
   * against the only route to the same total without the call: nhdfit_schedule_batch(apply=0) over replicas + 1 copies of the
     template, same mirror (`--route-only=R2,R4`: that leg alone, given the two totals - a copy of this file in a checkout of the parent
     commit, which has no nhdfit_headroom, gives the same-box comparison);
-  * one template on a cluster with no room at all (every node in maintenance) against nhdfit_find for the same pod.
+  * one template on a cluster with no room at all (every node in maintenance) against nhdfit_find for the same pod;
+  * `--limits`: on each of the three shapes nhdfit_headroom_limits as well, histogram only and with the per-node entries and stages,
+    and nhdfit_explain for the one pod beside it (the nearest existing price of one stage per node).
 
 `python tools/time_headroom.py` on the GPU box; kernel time from a separate
-`rocprofv3 --kernel-trace --stats -- python tools/time_headroom.py --kernels` run (headroom calls only)."""
+`rocprofv3 --kernel-trace --stats -- python tools/time_headroom.py --kernels` run (headroom calls only; with `--limits` the
+limits calls too: k_limit_stage beside k_headroom)."""
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -18,7 +21,7 @@ from nhd_amd.engine import Engine
 from workload import planes, refmodel, synth
 
 ROUTE = [a for a in sys.argv[1:] if a.startswith("--route-only=")]       # --route-only=<replicas c2>,<replicas c4>: the totals a full run printed
-ROUTE_ONLY, KERNELS = bool(ROUTE), "--kernels" in sys.argv
+ROUTE_ONLY, KERNELS, LIMITS = bool(ROUTE), "--kernels" in sys.argv, "--limits" in sys.argv
 TOTALS = dict(zip(("c2", "c4"), (int(x) for x in ROUTE[0].split("=")[1].split(",")))) if ROUTE else {}
 
 
@@ -28,6 +31,15 @@ def timed(fn, reps):
     for _ in range(reps):
         t0 = time.perf_counter(); fn(); xs.append((time.perf_counter() - t0) * 1e3)
     return {"ms_median": float(np.median(xs)), "ms_min": float(min(xs))}
+
+
+def limits_legs(r, eng, req, now, reps):
+    sums, _, hist, _ = eng.headroom_limits(req)
+    r["limits"] = {s: int(k) for s, k in zip(("NOT_CANDIDATE", "MAINTENANCE", "HUGEPAGES", "BUSY", "GPU", "CPU", "NIC", "PCI", "NUMA", "FITS"), hist[0]) if k}
+    r["limits_hist"] = timed(lambda: eng.headroom_limits(req), reps)
+    r["limits_per_node"] = timed(lambda: eng.headroom_limits(req, per_node=True), reps)
+    if not KERNELS:
+        r["explain_one"] = timed(lambda: eng.explain(req, now + 1.0e6), reps)
 
 
 def shape(cfg, n, want_gpu, full=False):
@@ -56,6 +68,8 @@ for key, cfg, n in (("c2", 2, 4096), ("c4", 4, 65536)):
                  form=int(sums["form"][0]))
         r["headroom_sums"] = timed(lambda: eng.headroom(req), 30)
         r["headroom_per_node"] = timed(lambda: eng.headroom(req, per_node=True), 30)
+        if LIMITS:
+            limits_legs(r, eng, req, spec.clock_now, 30)
     if not KERNELS:
         total = r["replicas"] if "replicas" in r else TOTALS[key]
         copies = np.repeat(req, total + 1)
@@ -68,6 +82,8 @@ if not ROUTE_ONLY:
     spec, pk, req, eng = shape(4, 65536, want_gpu=False, full=True)
     sums, _ = eng.headroom(req)
     out["c4_no_room"] = {"nodes": 65536, "replicas": int(sums["replicas"][0]), "headroom_sums": timed(lambda: eng.headroom(req), 50)}
+    if LIMITS:
+        limits_legs(out["c4_no_room"], eng, req, spec.clock_now, 50)
     if not KERNELS:
         out["c4_no_room"]["find_one"] = timed(lambda: eng.find(req, spec.clock_now, want_bitmap=False, want_map=True), 50)
     eng.close()
