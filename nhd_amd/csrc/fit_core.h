@@ -456,13 +456,30 @@ NHD_HD uint32_t pair_c_row(uint32_t cc, uint32_t D) {              // row of C f
 // Node.IsBusy (nhd/Node.py:847-850) is `(now - busy_time) < 30.0` in binary64.  fl(now - t) never increases with t,
 // so the busy nodes are exactly those with busy_time >= busy_threshold(now): one comparison per node instead of a
 // subtraction and a comparison, and still the reference's own arithmetic (the threshold is found with it).
+// The threshold is the smallest double the reference's predicate calls busy, found by bisection over the doubles in their
+// numeric order between -DBL_MAX (not busy) and DBL_MAX (busy): at most 64 evaluations of the predicate whatever `now` is.
+// (It can lie far from fl(now - 30.0) counted in doubles: with `now` within a quarter of a second of 30.0 that difference is
+// exact and small, so its neighbours lie far closer together than those of 30.0, and the predicate flips only about 2^-49 -
+// half an ulp of 30.0 - further on: thousands of doubles.  A walk of a fixed number of neighbours from fl(now - 30.0) stops
+// short there.)
+// No finite stamp busy (`now` = +inf, NaN): NaN, which no stamp is >=; every finite stamp busy (`now` near -DBL_MAX): -DBL_MAX.
 inline double busy_threshold(double now) {
-    double b = now - kMinBusySecs;
-    auto up = [](double x) { return __builtin_nextafter(x, __builtin_inf()); };
-    auto down = [](double x) { return __builtin_nextafter(x, -__builtin_inf()); };
-    for (int i = 0; i < 64 && !((now - b) < kMinBusySecs); ++i) b = up(b);
-    for (int i = 0; i < 64 && (now - down(b)) < kMinBusySecs; ++i) b = down(b);
-    return b;
+    constexpr uint64_t kSign = 1ull << 63, kMaxBits = 0x7FEFFFFFFFFFFFFFull;           // (bits of DBL_MAX)
+    auto at = [](uint64_t key) {                         // key -> double, keys ordered as the doubles are (-0.0 right below +0.0)
+        const uint64_t bits = key & kSign ? key ^ kSign : ~key;
+        double x;
+        __builtin_memcpy(&x, &bits, sizeof x);
+        return x;
+    };
+    auto is_busy = [now](double t) { return (now - t) < kMinBusySecs; };
+    uint64_t lo = ~(kMaxBits | kSign), hi = kMaxBits | kSign;                          // keys of -DBL_MAX, DBL_MAX
+    if (!is_busy(at(hi))) return __builtin_nan("");
+    if (is_busy(at(lo))) return at(lo);
+    while (hi - lo > 1) {                                // is_busy(at(lo)) is false, is_busy(at(hi)) is true
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if (is_busy(at(mid))) hi = mid; else lo = mid;
+    }
+    return at(hi);
 }
 
 NHD_HD uint64_t ld64(const uint8_t* img, uint32_t off) { return *reinterpret_cast<const uint64_t*>(img + off); }

@@ -60,6 +60,13 @@ def find(packer: pack.Packer, table: pack.NodeTable, reqs: np.ndarray, now: floa
     return score, bitmap, maps
 
 
+def busy_threshold(now: float) -> float:
+    """fit_core.h busy_threshold(now) of the host build: the `busy_from` every launch hands its kernels."""
+    L = lib()
+    L.hh_busy_threshold.restype = ctypes.c_double
+    return float(L.hh_busy_threshold(ctypes.c_double(now)))
+
+
 def typed_stream(packer: pack.Packer):
     """(words, pool types) of the dictionary's stream by pool type as nhdfit_set_dictionary builds it (dict_stream.h); 0 words: not in use."""
     L = lib()

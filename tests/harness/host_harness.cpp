@@ -73,6 +73,9 @@ void build_tile(const nhdfit_req* reqs, uint32_t npods, const Dict& d, const Lay
 
 extern "C" {
 
+// fit_core.h busy_threshold: the stamp from which on a node is busy at `now`, as every launch computes it on the host
+double hh_busy_threshold(double now) { return busy_threshold(now); }
+
 // words of the dictionary's stream by pool type (dict_stream.h), pool types in it; 0 words: the dictionary does not fit the format
 int hh_typed_stream(const uint32_t* sig_off, uint32_t nsig, const uint32_t* pool_off, const uint8_t* pool_glimit, const nhdfit_cc* cc,
                     uint32_t* ntypes) {
