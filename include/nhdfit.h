@@ -601,8 +601,8 @@ typedef struct {
     uint32_t form;                              /* NHDFIT_HEADROOM_FORM_*; 0: nothing was launched (an empty mirror)               */
 } nhdfit_headroom_sum;                          /* 32 bytes */
 /* sum_out [P]; counts_out: NULL, or [P][n] entries by node index.  cand as nhdfit_find.  A request of an invalid map type fits
- * nowhere (all zero), as nhdfit_find answers it.  nhdfit_big_req pods have no entry here.  NHDFIT_E_LIMIT: a dictionary whose
- * signature stream does not fit the block's LDS (more than 4096 NIC signatures), a hugepage request beyond the pod tile's. */
+ * nowhere (all zero), as nhdfit_find answers it.  nhdfit_big_req pods have no entry here.  NHDFIT_E_LIMIT: a dictionary of more
+ * than 4096 NIC signatures (or one whose signature stream is beyond 16-bit word offsets), a hugepage request beyond the pod tile's. */
 int nhdfit_headroom(nhdfit_ctx* ctx, const nhdfit_req* reqs, uint32_t P, const uint64_t* cand, uint32_t max_per_node,
                     nhdfit_headroom_sum* sum_out, uint16_t* counts_out);
 /* ... over every shard of a group: sum_out summed over the devices (max_on_one_node: the largest); counts_out NULL, or one

@@ -8,7 +8,7 @@
 // question is parallel over the nodes - a commit only ever changes its own node - and the pieces exist: find1_commit.h chains
 // find -> map -> commit once, for one node; this kernel runs that chain to exhaustion on a private copy of every node at once.
 //
-//   grid = (blocks, templates).  A block derives its template's masks in LDS (NHDFIT_LONE_POD_MASKS, step_kernel.h: k_find1's own text)
+//   grid = (blocks, templates).  A block derives its template's masks in LDS (NHDFIT_LONE_POD_MASKS_OF, step_kernel.h: k_find1's own text)
 //   and then takes 64-node chunks off the template's ticket counter until the tickets run out - nodes differ by orders of
 //   magnitude in work (0 replicas against hundreds), a fixed split would leave the chip waiting for one block.  The counter is a
 //   relaxed agent-scope fetch-add: it hands out work, it publishes nothing, no fence.  Per chunk:
@@ -113,7 +113,9 @@ __global__ __launch_bounds__(kHeadroomBlock) void k_headroom(HeadroomArgs a) {
     unsigned long long* s_tot = carve<unsigned long long>(lds, 8);       // [0] replicas [1] nodes with room [2] max [3] saturated [4] stopped [5] not evaluated
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
 
-    NHDFIT_LONE_POD_MASKS(kHeadroomBlock, tid, a.reqs + tpl, a.d, a.nsig, a.fc_dim, a.fg_dim)
+    // (a dictionary of many NIC signatures - nodes with a dozen NICs of several speeds, every state a commit can produce interned - has
+    // a stream beyond the LDS slice: the masks are then derived off global memory, once per block; nothing below reads the stream again)
+    NHDFIT_LONE_POD_MASKS_OF(kHeadroomBlock, tid, a.reqs + tpl, a.d, a.nsig, a.fc_dim, a.fg_dim, a.d.flat_words <= kDictLdsWords)
     if (tid < (uint32_t)NHDFIT_MAX_CLASSES) s_caps[tid] = tid < a.ncls ? a.d.caps[tid] : 0.0;
     if (tid < 8u) s_tot[tid] = 0ull;
     HeadroomCtx x;

@@ -2946,9 +2946,9 @@ int headroom_run(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, const uint64
     const uint32_t n = c->n;
     if (!n) return NHDFIT_OK;
     if (!c->ncls || !c->nsig) return fail(c, NHDFIT_E_STATE, "set the dictionary first (nhdfit_set_dictionary)");
-    if (!c->flat_words || c->flat_words > kDictLdsWords || c->nsig > kLoneMaxSigs)
-        return fail(c, NHDFIT_E_LIMIT, "headroom: the dictionary's signature stream (%u words, %u signatures) does not fit the block's LDS (%u words, %u signatures)",
-                    c->flat_words, c->nsig, kDictLdsWords, kLoneMaxSigs);
+    // (a stream of more than kDictLdsWords words is read where it lies, headroom_kernel.h; flat_words == 0: it does not fit 16-bit offsets)
+    if (!c->flat_words || c->nsig > kLoneMaxSigs)
+        return fail(c, NHDFIT_E_LIMIT, "headroom: the dictionary has %u NIC signatures (<= %u, in a stream of at most 65535 words)", c->nsig, kLoneMaxSigs);
     HIPCHK(c, hipSetDevice(c->dev));
     TRY(sync_all(c));             // (the mirror as the last call left it; steps in flight are drained, their results stay fetchable)
     const uint32_t chunks = (n + 63) / 64;

@@ -534,6 +534,9 @@ struct Find1NoTail {
 // a block barrier, with `r`, `valid`, `W` and `G` declared) - ONE text for every launch that answers for one pod against the nodes directly:
 // k_find1 and k_find1_commit below, k_headroom (headroom_kernel.h, one template per block).  Macros, not functions: pasted, the text
 // compiles in k_find1 to the machine code it always did (checked against the parent build when k_headroom arrived).
+// NHDFIT_LONE_POD_MASKS_OF takes one more argument, STAGED (block-uniform): the dictionary's stream is copied into `s_flat` and read
+// there - the only form k_find1 and k_find1_commit are launched in, a literal `true` for them - or, false, read where it lies in
+// global memory (k_headroom with a stream of more than kDictLdsWords words: each lane walks its own signature's record once).
 #define NHDFIT_LONE_LDS(lds) \
     nhdfit_req* s_req = carve<nhdfit_req>(lds, 1); \
     PodSums* s_sum = carve<PodSums>(lds, 1); \
@@ -547,10 +550,12 @@ struct Find1NoTail {
     uint16_t* s_r0 = carve<uint16_t>(lds, kLoneMaxSigs); \
     uint16_t* s_r1 = carve<uint16_t>(lds, kLoneMaxSigs); \
     unsigned long long* s_best = carve<unsigned long long>(lds, 8);
-#define NHDFIT_LONE_POD_MASKS(BLOCK, tid, REQ, D, NSIG, FC_DIM, FG_DIM) \
+#define NHDFIT_LONE_POD_MASKS(BLOCK, tid, REQ, D, NSIG, FC_DIM, FG_DIM) NHDFIT_LONE_POD_MASKS_OF(BLOCK, tid, REQ, D, NSIG, FC_DIM, FG_DIM, true)
+#define NHDFIT_LONE_POD_MASKS_OF(BLOCK, tid, REQ, D, NSIG, FC_DIM, FG_DIM, STAGED) \
     if (tid < sizeof(nhdfit_req) / 16) reinterpret_cast<uint4*>(s_req)[tid] = reinterpret_cast<const uint4*>((REQ))[tid]; \
-    for (uint32_t w = tid; w < (D).flat_words / 2; w += BLOCK)   /* (the stream is padded to an even word count) */ \
-        reinterpret_cast<uint32_t*>(s_flat)[w] = reinterpret_cast<const uint32_t*>((D).flat)[w]; \
+    if (STAGED) \
+        for (uint32_t w = tid; w < (D).flat_words / 2; w += BLOCK)   /* (the stream is padded to an even word count) */ \
+            reinterpret_cast<uint32_t*>(s_flat)[w] = reinterpret_cast<const uint32_t*>((D).flat)[w]; \
     __syncthreads(); \
     const nhdfit_req& r = *s_req; \
     const bool valid = req_valid(r); \
@@ -577,11 +582,18 @@ struct Find1NoTail {
         (u ? s_w1 : s_w0)[e] = valid ? (uint16_t)entry_w(*s_sum, u, smt != 0, c, m) : (uint16_t)0; \
     } \
     __syncthreads(); \
-    for (uint32_t sig = tid; sig < (NSIG); sig += BLOCK) {   /* lane = signature */ \
-        const uint32_t reach = valid ? sig_reach_flat(s_flat, (NSIG), sig, s_cover, W) : 0u; \
-        s_r0[sig] = (uint16_t)entry_r(reach, W, 0); \
-        s_r1[sig] = (uint16_t)entry_r(reach, W, 1); \
-    } \
+    if (STAGED) \
+        for (uint32_t sig = tid; sig < (NSIG); sig += BLOCK) {   /* lane = signature */ \
+            const uint32_t reach = valid ? sig_reach_flat(s_flat, (NSIG), sig, s_cover, W) : 0u; \
+            s_r0[sig] = (uint16_t)entry_r(reach, W, 0); \
+            s_r1[sig] = (uint16_t)entry_r(reach, W, 1); \
+        } \
+    else \
+        for (uint32_t sig = tid; sig < (NSIG); sig += BLOCK) {   /* the same off the stream in global memory */ \
+            const uint32_t reach = valid ? sig_reach_flat((D).flat, (NSIG), sig, s_cover, W) : 0u; \
+            s_r0[sig] = (uint16_t)entry_r(reach, W, 0); \
+            s_r1[sig] = (uint16_t)entry_r(reach, W, 1); \
+        } \
     __syncthreads();
 template <int BLOCK, class TAIL>
 __device__ __forceinline__ void find1_launch(const Find1Args& a, const TAIL& tail) {

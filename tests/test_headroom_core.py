@@ -7,7 +7,7 @@ import pytest
 
 from nhd_amd import pack
 from nhd_amd.matcher import HipMatcher
-from tests import explain_check, harness, util
+from tests import edge_check, explain_check, harness, util
 from tests.harness import headroom_twin
 from tests.harness.headroom_twin import HeadroomHarnessEngine, HeadroomWaveEngine
 from workload import planes, refmodel, synth
@@ -45,6 +45,19 @@ def test_wavefront_loop_equals_the_scalar_twin_on_random_clusters(seed):
     assert one_socket.any() and sum(int(x.per_node[one_socket].sum()) for x in a) > 0      # the one-NUMA-node shortcut is exercised
     forms = {x.form for x in a}
     assert forms == {pack.HEADROOM_FORM_WAVE, pack.HEADROOM_FORM_GENERIC}
+
+
+def test_wavefront_loop_equals_the_scalar_twin_at_the_edges_of_the_record_formats():
+    """workload/edge_inputs.py's clusters (sockets of 33..64 cores, 9..16 NICs per NUMA node, pods_used up to 3, free hugepages around
+    the tile's table) and pods; the runs that end at a commit the reference raises on included."""
+    replicas = stopped = 0
+    for seed in (2, 9, 12, 22, 30, 33):
+        descs, specs = edge_check.wave_case(seed)
+        a, b = _both(util.build_cluster(descs), [refmodel.make_topology(s) for s in specs], max_per_node=8)
+        _same(a, b)
+        replicas += sum(x.replicas for x in a)
+        stopped += sum(x.stopped for x in a)
+    assert replicas >= 40 and stopped >= 1, (replicas, stopped)
 
 
 @pytest.mark.parametrize("cfg", [2, 3, 4, 5])

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 from nhd_amd import pack
-from tests import harness, util
+from tests import edge_check, harness, util
 from workload import refmodel, synth
 
 
@@ -65,6 +65,21 @@ def test_wavefront_commit_equals_the_scalar_commit_on_random_clusters(seed):
     assert checked >= 20 and raised >= 1
 
 
+EDGE_SEEDS = [2, 9, 12, 22, 30, 33]                    # tools/soak_extreme.py's seeds with the most feasible pairs among 0..35; 30, 33: NIC-heavy
+
+
+def test_wavefront_commit_at_the_edges_of_the_record_formats():
+    """workload/edge_inputs.py's clusters: sockets of 33..64 cores (bits 32..63 of the lanes' core masks), 9..16 NICs and 8 GPUs per NUMA
+    node, pods_used up to 3 - the one-stage and the two-stage form against the scalar commit, repeated until the node runs dry."""
+    checked = raised = upper = 0
+    for seed in EDGE_SEEDS:
+        descs, specs = edge_check.wave_case(seed)
+        c, r = _run(util.build_cluster(descs), specs, repeats=4, seed=seed)
+        checked, raised = checked + c, raised + r
+        upper += sum(edge_check.E.upper_half_cores(d) for d in descs)
+    assert checked >= 100 and raised >= 30 and upper >= 12, (checked, raised, upper)
+
+
 def test_wavefront_commit_on_the_baseline_mixes():
     """config 4 (GPUs, NICs, PCI locality) and config 5 (eight VFs per NUMA node: the signature keys over many NICs)"""
     total = 0
@@ -116,6 +131,27 @@ def test_wavefront_mapping_equals_the_scalar_mapping(seed):
             pairs += 1
             mapped += ok == 3
     assert pairs >= 100 and mapped >= 5
+
+
+@pytest.mark.parametrize("seed", EDGE_SEEDS[:4])
+def test_wavefront_mapping_equals_the_scalar_mapping_at_the_edges(seed):
+    """The same on every (pod, fast-layout node) pair of an edge cluster (workload/edge_inputs.py), tables 0, 1 and 2."""
+    descs, specs = edge_check.wave_case(seed)
+    pk = pack.Packer()
+    table = pk.pack_nodes(util.build_cluster(descs))
+    reqs = pk.digest_many([refmodel.make_topology(s) for s in specs])
+    pk.close_signatures()
+    pairs = mapped = 0
+    for i in range(table.n):
+        if table.wide and i in table.wide:
+            continue
+        for p in range(len(reqs)):
+            for tables in (0, 1, 2):
+                rc, ok, ms, mw = harness.wave_map_on_state(pk, table, i, reqs[p], tables)
+                assert rc == 0, (rc, ok, i, specs[p], ms, mw, tables)
+            pairs += 1
+            mapped += ok == 3
+    assert pairs >= 100 and mapped >= 5, (pairs, mapped)
 
 
 @pytest.mark.parametrize("seed", range(3))
