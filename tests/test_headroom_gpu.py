@@ -68,22 +68,7 @@ def test_golden_entries_equal_the_reference(golden, with_groups):
 
 
 # ---- BASELINE shapes against the independent oracle -------------------------------------------------------------------------------------
-def four_templates(cfg):
-    """Four templates of the configuration's own pods that cover one, two, three and four processing groups (the fourth is put
-    together from the three-group one and a group of the one-group one, in the other map type), and - where the configuration draws
-    them - pods with and without GPUs, NUMA and PCI mode."""
-    specs, _ = synth.make_pods(cfg, n_pods=256)
-
-    def pick(G, gpu, pci):
-        def score(s):
-            has_gpu = any(g["gpus"] for g in s["groups"])
-            return (has_gpu == gpu) + (((s["map_type"] == "PCI") == pci))
-        return max((s for s in specs if len(s["groups"]) == G), key=score)
-    one, two, three = pick(1, True, True), pick(2, False, False), pick(3, True, False)
-    four = dict(three, groups=[dict(g) for g in three["groups"]] + [dict(one["groups"][0])], map_type="PCI" if three["map_type"] == "NUMA" else "NUMA")
-    if cfg == 2:                                             # (the configuration draws NUMA pods only, and no GPUs)
-        four["map_type"] = "NUMA"
-    return [one, two, three, four]
+four_templates = hc.four_templates          # (tests/headroom_check.py: the CPU suite takes them from there)
 
 
 def engine_for(cfg, n, specs, groups=None):
