@@ -610,6 +610,31 @@ int nhdfit_headroom(nhdfit_ctx* ctx, const nhdfit_req* reqs, uint32_t P, const u
 int nhdfit_group_headroom(nhdfit_group* g, const nhdfit_req* reqs, uint32_t P, const uint64_t* const* cand, uint32_t max_per_node,
                           nhdfit_headroom_sum* sum_out, uint16_t* const* counts_out);
 
+/* ---- headroom on the general path: wide records and ENABLE_SHARING mirrors (opt-in) ----------------------------------
+ * nhdfit_headroom with a figure for every candidate the mirror holds as a wide record (3 or 4 sockets, 65..128 physical cores per
+ * socket, every node of an ENABLE_SHARING mirror) instead of NHDFIT_HEADROOM_NOT_EVALUATED.  The semantics are nhdfit_headroom's: the
+ * number of times FindNode on the one node (nhd/NHDScheduler.py:277, nhd/Matcher.py:65-391 by enumeration over
+ * itertools.product(range(numa_nodes), ...), :118, :203, :242) -> SetPhysicalIdsFromMapping (:292, nhd/Node.py:663-841) ->
+ * ClaimPodNICResources (:302-304, nhd/Node.py:644-646) succeeds back to back on a private copy of the record, IsBusy() false.
+ * Under ENABLE_SHARING the private copy includes the node's nhdfit_wide_share record: the commit step adds each group's RX / TX
+ * speed to speed_used in group order (nhd/Node.py:754), and the next replica is priced at speed * 0.9 - speed_used
+ * (nhd/Node.py:289-291) - several replicas on one NIC are the point of the switch.  A commit the reference raises on
+ * (nhd/Node.py:686) ends the run: count | NHDFIT_HEADROOM_STOPPED.
+ * Entries and sums of the nodes of the planes are nhdfit_headroom's, bit for bit; a wide candidate's entry is its count, it is part
+ * of replicas / nodes_with_room / max_on_one_node / saturated / stopped, and not_evaluated no longer counts it.  On a mirror without
+ * wide records the output is nhdfit_headroom's byte for byte (`form` included: the wide launch is skipped).  Nothing is written:
+ * not the wide records, not the share records, not the planes, busy times, staged batch or nhdfit_get_stats.
+ * Not covered: nhdfit_big_req templates (no entry here), limits (nhdfit_headroom_limits is the planes' alone), nodes neither
+ * layout holds.  NHDFIT_E_LIMIT: nhdfit_headroom's cases - they hold on a pure ENABLE_SHARING mirror as well, whose planes are
+ * placeholders: the planes' launch runs first on every mirror and flags the candidates, one rule instead of two - and a set of the
+ * general set model that outgrew its table (never expected; as nhdfit_find reports it): sum_out and counts_out are then all zero. */
+#define NHDFIT_HEADROOM_FORM_WIDE     4u        /* OR-ed into `form`: the launch over the wide records ran                         */
+int nhdfit_headroom_general(nhdfit_ctx* ctx, const nhdfit_req* reqs, uint32_t P, const uint64_t* cand, uint32_t max_per_node,
+                            nhdfit_headroom_sum* sum_out, uint16_t* counts_out);
+/* ... over every shard of a group, as nhdfit_group_headroom (`form`: the planes' value as there, the wide bit if any shard ran it). */
+int nhdfit_group_headroom_general(nhdfit_group* g, const nhdfit_req* reqs, uint32_t P, const uint64_t* const* cand, uint32_t max_per_node,
+                                  nhdfit_headroom_sum* sum_out, uint16_t* const* counts_out);
+
 /* ---- headroom limits: the stage that ends each node's run -------------------------------------------------------------
  * nhdfit_headroom with one more answer per (template, node): which resource ran out.  limit(node, template) is the stage
  * nhdfit_explain's stage function (NHDFIT_STAGE_*, nhd/Matcher.py:65-391) names for the template on the node IN THE STATE IN

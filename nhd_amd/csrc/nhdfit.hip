@@ -66,6 +66,7 @@ namespace {
 #include "explain_kernel.h"
 #include "headroom_kernel.h"
 #include "limit_kernel.h"
+#include "wide_room_kernel.h"
 
 // ------------------------------------------------------------------------------------------------
 // host side
@@ -279,6 +280,8 @@ struct nhdfit_ctx {
     DevBuf<nhdfit_req> hr_reqs; DevBuf<uint32_t> hr_tickets; DevBuf<HeadroomSum> hr_sum; DevBuf<uint16_t> hr_counts; DevBuf<uint64_t> hr_cand;
     // nhdfit_headroom_limits (limit_kernel.h): the runs' final states, a slab of templates at a time, and the stage histogram / matrix
     DevBuf<HeadroomFinal> hr_final; DevBuf<uint32_t> hr_hist; DevBuf<uint8_t> hr_stage;
+    // nhdfit_headroom_general (wide_room_kernel.h): the wide launch's ticket counters, and behind them its flag words
+    DevBuf<uint32_t> hr_wide_tickets;
     int wide_slot(uint32_t node) const {
         auto it = std::lower_bound(wide_index.begin(), wide_index.end(), node);
         return it != wide_index.end() && *it == node ? (int)(it - wide_index.begin()) : -1;
@@ -571,7 +574,7 @@ void nhdfit_destroy(nhdfit_ctx* c) {
     c->big_cand.release(); c->big_scratch.release();
     c->ex_views.release(); c->ex_slot.release(); c->ex_reqs.release(); c->ex_big_reqs.release(); c->ex_counts.release(); c->ex_flags.release();
     c->ex_cand.release(); c->ex_stage.release();
-    c->hr_reqs.release(); c->hr_tickets.release(); c->hr_sum.release(); c->hr_counts.release(); c->hr_cand.release();
+    c->hr_reqs.release(); c->hr_tickets.release(); c->hr_sum.release(); c->hr_counts.release(); c->hr_cand.release(); c->hr_wide_tickets.release();
     if (c->find_host) (void)hipHostFree(c->find_host);
     if (c->commit_host) (void)hipHostFree(c->commit_host);
     c->commit_host = nullptr;
@@ -2932,9 +2935,11 @@ int nhdfit_group_explain(nhdfit_group* g, const nhdfit_req* reqs, uint32_t P, do
 }  // extern "C"
 namespace {
 // nhdfit_headroom (limits_out == nullptr: one launch over every template, nothing kept) and nhdfit_headroom_limits (the templates in
-// slabs of `slab_bytes` of final states; per slab k_headroom with HeadroomArgs::final, then k_limit_stage on what it left)
+// slabs of `slab_bytes` of final states; per slab k_headroom with HeadroomArgs::final, then k_limit_stage on what it left).
+// `general` (nhdfit_headroom_general, no limits): behind k_headroom, k_wide_room over (template, wide record) on the same stream - it
+// overwrites the entries k_headroom flagged NOT_EVALUATED and corrects the sums; skipped on a mirror without wide records.
 int headroom_run(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, const uint64_t* cand, uint32_t max_per_node, nhdfit_headroom_sum* sum_out,
-                 uint16_t* counts_out, uint32_t* limits_out, uint8_t* stage_out, size_t slab_bytes) {
+                 uint16_t* counts_out, uint32_t* limits_out, uint8_t* stage_out, size_t slab_bytes, bool general = false) {
     if (!reqs || !P || !sum_out) return fail(c, NHDFIT_E_INVAL, "headroom: requests and sum_out are required");
     if (!max_per_node || max_per_node > NHDFIT_HEADROOM_COUNT_MASK)
         return fail(c, NHDFIT_E_INVAL, "headroom: max_per_node is %u (1 .. %u)", max_per_node, (unsigned)NHDFIT_HEADROOM_COUNT_MASK);
@@ -3017,17 +3022,49 @@ int headroom_run(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, const uint64
         HIPCHK(c, hipMemcpyAsync(limits_out, c->hr_hist.p, (size_t)P * NHDFIT_STAGES * sizeof(uint32_t), hipMemcpyDeviceToHost, c->streams.use(0)));
         if (stage_out) HIPCHK(c, hipMemcpyAsync(stage_out, c->hr_stage.p, (size_t)P * n, hipMemcpyDeviceToHost, c->streams.use(0)));
     }
+    const bool wide_ran = general && !limits_out && c->n_wide != 0;
+    uint32_t wide_flags[4] = {0, 0, 0, 0};
+    if (wide_ran) {
+        const uint32_t wchunks = (c->n_wide + 63) / 64;
+        HIPCHK(c, c->hr_wide_tickets.reserve((size_t)P + 4));
+        HIPCHK(c, hipMemsetAsync(c->hr_wide_tickets.p, 0, ((size_t)P + 4) * sizeof(uint32_t), c->streams.use(0)));
+        WideRoomArgs wa;
+        memset(&wa, 0, sizeof wa);
+        wa.wide = c->wide.p; wa.n_wide = c->n_wide; wa.share = c->sharing ? c->wide_share.p : nullptr;
+        wa.reqs = c->hr_reqs.p; wa.caps = c->caps.p; wa.ncls = c->ncls;
+        wa.cand = cand ? c->hr_cand.p : nullptr;
+        wa.n = n; wa.wchunks = wchunks; wa.cap = max_per_node; wa.pitch = pitch;
+        wa.tickets = c->hr_wide_tickets.p; wa.counts = c->hr_counts.p; wa.sum = c->hr_sum.p; wa.flags = c->hr_wide_tickets.p + P;
+        // blocks (of one wavefront, three to a CU: 41 KB of LDS each) per template: the chip's slots shared out among the templates, at most
+        // one per record - a record's run is the unit of work, and the runs differ by orders of magnitude
+        const uint32_t wslots = 3u * (uint32_t)c->prop.multiProcessorCount;
+        const uint32_t wb = std::max(1u, std::min(wchunks, (wslots + P - 1) / P));
+        hipLaunchKernelGGL(k_wide_room, dim3(wb, P), dim3(kWideRoomBlock), 0, c->streams.use(0), wa);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(wide_flags, c->hr_wide_tickets.p + P, sizeof wide_flags, hipMemcpyDeviceToHost, c->streams.use(0)));
+    }
     static_assert(sizeof(HeadroomSum) == sizeof(nhdfit_headroom_sum), "copied out as it is");
     HIPCHK(c, hipMemcpyAsync(sum_out, c->hr_sum.p, (size_t)P * sizeof *sum_out, hipMemcpyDeviceToHost, c->streams.use(0)));
     if (counts_out)
         HIPCHK(c, hipMemcpy2DAsync(counts_out, (size_t)n * sizeof(uint16_t), c->hr_counts.p, pitch * sizeof(uint16_t), (size_t)n * sizeof(uint16_t), P,
                                    hipMemcpyDeviceToHost, c->streams.use(0)));
     HIPCHK(c, c->streams.wait(0));
-    for (uint32_t p = 0; p < P; ++p) sum_out[p].form = form[p];
+    if (wide_flags[0]) {                                                 // (never expected) no half-corrected figures go out with the error
+        memset(sum_out, 0, (size_t)P * sizeof *sum_out);
+        if (counts_out) memset(counts_out, 0, (size_t)P * n * sizeof(uint16_t));
+        return fail(c, NHDFIT_E_LIMIT, "the set model of a wide node's mapping outgrew its table");
+    }
+    for (uint32_t p = 0; p < P; ++p) sum_out[p].form = form[p] | (wide_ran ? NHDFIT_HEADROOM_FORM_WIDE : 0u);
     return NHDFIT_OK;
 }
 }  // namespace
 extern "C" {
+
+int nhdfit_headroom_general(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, const uint64_t* cand, uint32_t max_per_node, nhdfit_headroom_sum* sum_out,
+                            uint16_t* counts_out) {
+    if (!c) return NHDFIT_E_INVAL;
+    return headroom_run(c, reqs, P, cand, max_per_node, sum_out, counts_out, nullptr, nullptr, 0, /*general=*/true);
+}
 
 int nhdfit_headroom(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, const uint64_t* cand, uint32_t max_per_node, nhdfit_headroom_sum* sum_out,
                     uint16_t* counts_out) {
@@ -3060,7 +3097,8 @@ void add_headroom_sums(nhdfit_headroom_sum* sum_out, const nhdfit_headroom_sum* 
         s.replicas += part[p].replicas; s.nodes_with_room += part[p].nodes_with_room; s.saturated += part[p].saturated;
         s.stopped += part[p].stopped; s.not_evaluated += part[p].not_evaluated;
         s.max_on_one_node = std::max(s.max_on_one_node, part[p].max_on_one_node);
-        s.form = std::max(s.form, part[p].form);
+        // (the planes' instantiation: the larger; the wide launch's bit: whether any shard ran it)
+        s.form = std::max(s.form & 3u, part[p].form & 3u) | ((s.form | part[p].form) & NHDFIT_HEADROOM_FORM_WIDE);
     }
 }
 }  // namespace
@@ -3075,6 +3113,20 @@ int nhdfit_group_headroom(nhdfit_group* g, const nhdfit_req* reqs, uint32_t P, c
     for (size_t k = 0; k < g->ctx.size(); ++k) {
         nhdfit_ctx* c = g->ctx[k];
         const int rc = nhdfit_headroom(c, reqs, P, cand ? cand[k] : nullptr, max_per_node, part.data(), counts_out ? counts_out[k] : nullptr);
+        if (rc) { g->err = c->err; return rc; }
+        add_headroom_sums(sum_out, part.data(), P);
+    }
+    return NHDFIT_OK;
+}
+
+int nhdfit_group_headroom_general(nhdfit_group* g, const nhdfit_req* reqs, uint32_t P, const uint64_t* const* cand, uint32_t max_per_node,
+                                  nhdfit_headroom_sum* sum_out, uint16_t* const* counts_out) {
+    if (!g || !reqs || !P || !sum_out) return NHDFIT_E_INVAL;
+    std::vector<nhdfit_headroom_sum> part(P);
+    memset(sum_out, 0, (size_t)P * sizeof *sum_out);
+    for (size_t k = 0; k < g->ctx.size(); ++k) {
+        nhdfit_ctx* c = g->ctx[k];
+        const int rc = nhdfit_headroom_general(c, reqs, P, cand ? cand[k] : nullptr, max_per_node, part.data(), counts_out ? counts_out[k] : nullptr);
         if (rc) { g->err = c->err; return rc; }
         add_headroom_sums(sum_out, part.data(), P);
     }

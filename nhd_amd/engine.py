@@ -307,7 +307,8 @@ class Engine:
         return counts, stages
 
     # ---- headroom: how many more replicas of each template every node can take (nhdfit_headroom) ------------------------------
-    def headroom(self, reqs: np.ndarray, cand: Optional[np.ndarray] = None, max_per_node: int = 512, per_node: bool = False):
+    def headroom(self, reqs: np.ndarray, cand: Optional[np.ndarray] = None, max_per_node: int = 512, per_node: bool = False,
+                 _general: bool = False):
         """(sums [P] pack.HEADROOM_SUM, entries [P][n] uint16 or None) for ordinary requests (pack.REQ): per node the replicas that
         fit back to back (pack.HEADROOM_COUNT_MASK) and the STOPPED / NOT_EVALUATED bits.  Nodes outside `cand` have 0; nothing of
         the mirror changes."""
@@ -319,8 +320,14 @@ class Engine:
             cand = np.ascontiguousarray(cand, dtype=np.uint64)
             assert cand.shape == ((self.n + 63) // 64,)
         if P:
-            self._chk(self.lib.nhdfit_headroom(self.ctx, _p(reqs), P, _p(cand), int(max_per_node), _p(sums), _p(counts)))
+            fn = self.lib.nhdfit_headroom_general if _general else self.lib.nhdfit_headroom
+            self._chk(fn(self.ctx, _p(reqs), P, _p(cand), int(max_per_node), _p(sums), _p(counts)))
         return sums, counts
+
+    def headroom_general(self, reqs: np.ndarray, cand: Optional[np.ndarray] = None, max_per_node: int = 512, per_node: bool = False):
+        """headroom() with a figure for every candidate held as a wide record - wide nodes, every node of an ENABLE_SHARING mirror -
+        instead of NOT_EVALUATED (nhdfit_headroom_general); the nodes of the planes are answered as headroom() answers them."""
+        return self.headroom(reqs, cand=cand, max_per_node=max_per_node, per_node=per_node, _general=True)
 
     def headroom_limits(self, reqs: np.ndarray, cand: Optional[np.ndarray] = None, max_per_node: int = 512, per_node: bool = False,
                         _slab_bytes: Optional[int] = None):
@@ -750,7 +757,12 @@ class GroupEngine:
                     stages[:, lo:hi] = st
         return counts, stages
 
-    def headroom(self, reqs: np.ndarray, cand: Optional[np.ndarray] = None, max_per_node: int = 512, per_node: bool = False):
+    def headroom_general(self, reqs: np.ndarray, cand: Optional[np.ndarray] = None, max_per_node: int = 512, per_node: bool = False):
+        """Engine.headroom_general over every shard (nhdfit_group_headroom_general), as headroom()."""
+        return self.headroom(reqs, cand=cand, max_per_node=max_per_node, per_node=per_node, _general=True)
+
+    def headroom(self, reqs: np.ndarray, cand: Optional[np.ndarray] = None, max_per_node: int = 512, per_node: bool = False,
+                 _general: bool = False):
         """Engine.headroom over every shard: the sums added over the devices (nhdfit_group_headroom), the entries put together in
         global node order."""
         reqs = np.ascontiguousarray(reqs, dtype=pack.REQ)
@@ -766,8 +778,8 @@ class GroupEngine:
             parts = [np.zeros((P, hi - lo), np.uint16) if per_node and hi > lo else None for lo, hi in self._bounds]
             cptr = (ctypes.c_void_p * len(self.shards))(*[None if m is None else m.ctypes.data for m in masks])
             sptr = (ctypes.c_void_p * len(self.shards))(*[None if x is None else x.ctypes.data for x in parts])
-            rc = self.lib.nhdfit_group_headroom(self.group, _p(reqs), P, cptr if cand is not None else None, int(max_per_node), _p(sums),
-                                                sptr if per_node else None)
+            fn = self.lib.nhdfit_group_headroom_general if _general else self.lib.nhdfit_group_headroom
+            rc = fn(self.group, _p(reqs), P, cptr if cand is not None else None, int(max_per_node), _p(sums), sptr if per_node else None)
             if rc != 0:
                 raise _lib.NhdFitError(rc, (self.lib.nhdfit_group_last_error(self.group) or b"?").decode())
         else:
@@ -775,7 +787,8 @@ class GroupEngine:
             for k, s in enumerate(self.shards):
                 lo, hi = self._bounds[k]
                 if hi > lo:
-                    sm, ct = s.headroom(reqs, cand=masks[k], max_per_node=max_per_node, per_node=per_node)
+                    call = s.headroom_general if _general else s.headroom
+                    sm, ct = call(reqs, cand=masks[k], max_per_node=max_per_node, per_node=per_node)
                     _add_headroom_sums(sums, sm)
                     parts.append(ct)
                 else:
@@ -882,7 +895,8 @@ def _add_headroom_sums(sums: np.ndarray, part: np.ndarray) -> None:
     for f in ("replicas", "nodes_with_room", "saturated", "stopped", "not_evaluated"):
         sums[f] += part[f]
     sums["max_on_one_node"] = np.maximum(sums["max_on_one_node"], part["max_on_one_node"])
-    sums["form"] = np.maximum(sums["form"], part["form"])
+    # (the planes' instantiation: the larger; the wide launch's bit: whether any shard ran it)
+    sums["form"] = np.maximum(sums["form"] & 3, part["form"] & 3) | ((sums["form"] | part["form"]) & pack.HEADROOM_FORM_WIDE)
 
 
 def winner_index(score: int) -> int:

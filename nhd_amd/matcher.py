@@ -843,24 +843,33 @@ class HipMatcher:
         return out
 
     def Headroom(self, nl: Dict[str, object], top, pod_groups: Optional[Sequence[str]] = None, per_node: bool = False,
-                 max_per_node: int = 512, strict: Optional[bool] = None, limits: bool = False) -> Headroom:
+                 max_per_node: int = 512, strict: Optional[bool] = None, limits: bool = False, general: bool = False) -> Headroom:
         """HeadroomMany for one pod template."""
         return self.HeadroomMany(nl, [top], None if pod_groups is None else [pod_groups], per_node=per_node, max_per_node=max_per_node,
-                                 strict=strict, limits=limits)[0]
+                                 strict=strict, limits=limits, general=general)[0]
 
     def HeadroomMany(self, nl: Dict[str, object], tops: Sequence[object], pod_groups: Optional[Sequence[Sequence[str]]] = None,
-                     per_node: bool = False, max_per_node: int = 512, strict: Optional[bool] = None, limits: bool = False) -> List[Headroom]:
+                     per_node: bool = False, max_per_node: int = 512, strict: Optional[bool] = None, limits: bool = False,
+                     general: bool = False) -> List[Headroom]:
         """How many more replicas of each pod template of `tops` the nodes of `nl` can take, counted on the device (nhdfit_headroom):
         per node the number of times FindNode -> SetPhysicalIdsFromMapping -> ClaimPodNICResources succeeds back to back on a private
         copy of the node, busy windows out of the way (capacity, not rate: there is no `now`).  The mirror state is the one
         FindNodes(nl, tops, pod_groups) answers from (pending changes are flushed the same way); nothing about it changes.
-        `max_per_node` (1..16383) bounds a node's run - a template that asks for nothing would fit for ever.  Wide nodes and
-        ENABLE_SHARING mirrors are reported as not evaluated, never as a number.  A template no request record can express (5..8
+        `max_per_node` (1..16383) bounds a node's run - a template that asks for nothing would fit for ever.  Without
+        `general`, wide nodes and ENABLE_SHARING mirrors are reported as not evaluated, never as a number.  A template no request record can express (5..8
         processing groups, hugepages beyond the pod tile, an unsupported request) or a device error comes back with `error` set
         and everything not evaluated - `strict=True` (default: the matcher's) raises instead.
         limits=True (nhdfit_headroom_limits): the same figures and, per template, the stage that ended each node's run - the stage
         ExplainNode would name for the template on the node in the state its last replica left it, nothing busy (Headroom.limits,
-        Headroom.limit_stages, Headroom.limit_summary())."""
+        Headroom.limit_stages, Headroom.limit_summary()).
+        general=True (nhdfit_headroom_general): wide nodes and the nodes of an ENABLE_SHARING mirror are counted as well - the same
+        sequence on a private copy of the node's wide record and, under ENABLE_SHARING, of its NICs' speed_used, so that each replica
+        is priced against what the earlier ones use - and are part of every sum; the other nodes are answered exactly as without it.
+        What the packer refuses under ENABLE_SHARING (several RX / TX cores of a group at speeds that do not add exactly) stays
+        refused, templates of 5..8 processing groups still come back with `error`, and limits=True is not available with it
+        (ValueError)."""
+        if general and limits:
+            raise ValueError("general=True and limits=True: the limits are answered for the fast layout only (nhdfit_headroom_limits)")
         strict = self.strict if strict is None else strict
         n_pods = len(tops)
         if n_pods == 0:
@@ -908,6 +917,8 @@ class HipMatcher:
                         bits[off] = False
                         cand = np.ascontiguousarray(np.packbits(bits.reshape(-1, 64), axis=1, bitorder="little").view("<u8").reshape(-1))
                     sums, counts, hist, stages = self.engine.headroom_limits(reqs, cand=cand, max_per_node=int(max_per_node), per_node=per_node)
+                elif general:
+                    sums, counts = self.engine.headroom_general(reqs, cand=cand, max_per_node=int(max_per_node), per_node=per_node)
                 else:
                     sums, counts = self.engine.headroom(reqs, cand=cand, max_per_node=int(max_per_node), per_node=per_node)
             except NhdFitError as e:
