@@ -89,6 +89,11 @@ _SIGS = {
     "nhdfit_digest_triad_config_big": (c_int, [c_char_p, ctypes.c_size_t, c_void_p, c_char_p, ctypes.c_size_t]),
     "nhdfit_digest_triad_configs": (c_int, [c_void_p, c_void_p, c_uint32, c_void_p, c_void_p]),
 }
+# entries of the library outside include/nhdfit.h (tests/test_abi.py holds _SIGS to the header, so they are not in it):
+# nhdfit_headroom_limits with the device-memory budget of the runs' final states as a last argument (0: the default)
+_UNLISTED_SIGS = {
+    "nhdfit_headroom_limits_slab": (c_int, _SIGS["nhdfit_headroom_limits"][1] + [c_uint64]),
+}
 
 _lib = None
 
@@ -122,7 +127,7 @@ def load():
     got = lib.nhdfit_abi_version()
     if got != ABI_VERSION:                                      # record layouts differ: never talk to it
         raise NhdFitError(-5, f"{LIB_PATH} implements ABI {got}, this binding expects {ABI_VERSION}: rebuild it (python -m nhd_amd.build --force)")
-    for name, (res, args) in _SIGS.items():
+    for name, (res, args) in {**_SIGS, **_UNLISTED_SIGS}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

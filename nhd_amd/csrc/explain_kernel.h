@@ -26,6 +26,23 @@ __global__ __launch_bounds__(kExplainThreads) void k_explain_views(ExplainViewAr
     if (s < 0) wide_view(a.p0[v], a.p1[v], a.p2[v], a.p3[v], a.p4[v], a.det[v], v, a.views[v]);
 }
 
+// The stage histogram of one (block, pod): every wavefront ballots each stage, the wavefronts' counts meet in LDS (`cnt`), and one
+// thread per stage posts ONE atomicAdd into row `pod` of `hist`.  `st`: the lane's stage (NHDFIT_STAGES and beyond: counted nowhere).
+// Ends with `cnt` still being read: the caller puts a barrier in front of its next use.  (k_explain; k_limit_stage, limit_kernel.h.)
+template <uint32_t kWaves>
+__device__ __forceinline__ void stage_histogram(uint32_t (*cnt)[NHDFIT_STAGES], uint32_t st, uint32_t* hist, uint32_t pod, uint32_t tid) {
+    for (uint32_t k = 0; k < NHDFIT_STAGES; ++k) {
+        const uint64_t m = __ballot(st == k);
+        if ((tid & 63u) == 0) cnt[tid >> 6][k] = (uint32_t)popc64(m);
+    }
+    __syncthreads();
+    if (tid < NHDFIT_STAGES) {
+        uint32_t sum = 0;
+        for (uint32_t w = 0; w < kWaves; ++w) sum += cnt[w][tid];
+        if (sum) atomicAdd(&hist[(size_t)pod * NHDFIT_STAGES + tid], sum);
+    }
+}
+
 template <class R> struct ExplainArgs {
     const nhdfit_wide_node* views; const int32_t* slot; uint32_t n;
     const nhdfit_wide_node* wide;
@@ -42,7 +59,7 @@ template <class R> __global__ __launch_bounds__(kExplainThreads) void k_explain(
     __shared__ uint32_t s_cnt[kExplainThreads / 64][NHDFIT_STAGES];
     __shared__ R s_req;                                                // the pod's record: its fields reach the lanes as VGPRs (read
                                                                        // from the kernel argument's pointer they would be held in SGPRs)
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t tid = threadIdx.x;
     const uint32_t v = blockIdx.x * kExplainThreads + tid;
     const bool live = v < a.n;
     const int s = live ? a.slot[v] : -1;
@@ -62,16 +79,7 @@ template <class R> __global__ __launch_bounds__(kExplainThreads) void k_explain(
             if (out) atomicOr(&a.flags[0], 1u);
             if (a.stage) a.stage[(size_t)i * a.n + v] = (uint8_t)st;
         }
-        for (uint32_t k = 0; k < NHDFIT_STAGES; ++k) {
-            const uint64_t m = __ballot(st == k);
-            if (lane == 0) s_cnt[wave][k] = (uint32_t)popc64(m);
-        }
-        __syncthreads();
-        if (tid < NHDFIT_STAGES) {
-            uint32_t sum = 0;
-            for (uint32_t w = 0; w < kExplainThreads / 64; ++w) sum += s_cnt[w][tid];
-            if (sum) atomicAdd(&a.counts[(size_t)i * NHDFIT_STAGES + tid], sum);
-        }
+        stage_histogram<kExplainThreads / 64>(s_cnt, st, a.counts, i, tid);
         __syncthreads();                                               // (s_cnt and s_req are the next pod's)
     }
 }

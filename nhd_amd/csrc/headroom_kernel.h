@@ -71,6 +71,37 @@ static_assert(sizeof(HeadroomFinal) == 208 && sizeof(HeadroomFinal) % 16 == 0, "
 struct HeadroomSum { unsigned long long replicas; uint32_t nodes_with_room, max_on_one_node, saturated, stopped, not_evaluated, form; };
 static_assert(sizeof(HeadroomSum) == sizeof(nhdfit_headroom_sum) && sizeof(HeadroomSum) == 32, "the summary record of include/nhdfit.h");
 
+// A block's partial sums of one template, in LDS (eight words, zeroed by the block): [0] replicas [1] nodes with room [2] max
+// [3] saturated [4] stopped [5] the launch's own count - nodes k_headroom leaves not evaluated, nodes k_wide_room evaluates after all.
+// (The host twin's statement of the tally: hrh::account, tests/harness/headroom_host.h.)
+struct HeadroomTally {
+    unsigned long long* tot;
+    // one chunk: every lane of ONE wavefront brings its node's entry `e`; `sixth`: the chunk's nodes that count in slot 5 (wavefront-uniform)
+    __device__ __forceinline__ void chunk(uint32_t e, uint32_t cap, uint64_t sixth, uint32_t lane) const {
+        const uint32_t k = e & NHDFIT_HEADROOM_COUNT_MASK;
+        if (k) { atomicAdd(&tot[0], (unsigned long long)k); atomicMax(&tot[2], (unsigned long long)k); }
+        const uint64_t room = __ballot(k != 0u), sat = __ballot(k != 0u && k >= cap), stp = __ballot((e & NHDFIT_HEADROOM_STOPPED) != 0u);
+        if (lane == 0u) {
+            tot[1] += (unsigned long long)popc64(room); tot[3] += (unsigned long long)popc64(sat);
+            tot[4] += (unsigned long long)popc64(stp); tot[5] += (unsigned long long)popc64(sixth);
+        }
+    }
+    // the end of the block, behind its barrier, threads 0..5: one atomic per (block, template, field).  kTakeBack: slot 5 is taken out of
+    // not_evaluated (k_headroom counted those nodes; they have a figure now) instead of added to it
+    template <bool kTakeBack>
+    __device__ __forceinline__ void flush(HeadroomSum* q, uint32_t t) const {
+        if (t >= 6u || !tot[t]) return;
+        const unsigned long long v = tot[t];
+        if (t == 0u) atomicAdd(&q->replicas, v);
+        else if (t == 1u) atomicAdd(&q->nodes_with_room, (uint32_t)v);
+        else if (t == 2u) atomicMax(&q->max_on_one_node, (uint32_t)v);
+        else if (t == 3u) atomicAdd(&q->saturated, (uint32_t)v);
+        else if (t == 4u) atomicAdd(&q->stopped, (uint32_t)v);
+        else if (kTakeBack) atomicSub(&q->not_evaluated, (uint32_t)v);
+        else atomicAdd(&q->not_evaluated, (uint32_t)v);
+    }
+};
+
 struct HeadroomArgs {
     const nhdfit_plane0* p0; const nhdfit_plane1* p1; const nhdfit_plane2* p2; const nhdfit_plane3* p3; const nhdfit_plane4* p4;
     const nhdfit_detail* det; uint32_t n;
@@ -110,7 +141,7 @@ __global__ __launch_bounds__(kHeadroomBlock) void k_headroom(HeadroomArgs a) {
     double* s_caps = carve<double>(lds, NHDFIT_MAX_CLASSES);
     uint32_t* s_cnt = carve<uint32_t>(lds, 64);                          // the chunk's entries
     uint32_t* s_tick = carve<uint32_t>(lds, 4);
-    unsigned long long* s_tot = carve<unsigned long long>(lds, 8);       // [0] replicas [1] nodes with room [2] max [3] saturated [4] stopped [5] not evaluated
+    unsigned long long* s_tot = carve<unsigned long long>(lds, 8);       // the block's partial sums (HeadroomTally)
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
 
     // (a dictionary of many NIC signatures - nodes with a dozen NICs of several speeds, every state a commit can produce interned - has
@@ -183,25 +214,10 @@ __global__ __launch_bounds__(kHeadroomBlock) void k_headroom(HeadroomArgs a) {
         if (wave == 0u) {
             const uint32_t e = s_cnt[lane] | ((off_word >> lane & 1ull) ? NHDFIT_HEADROOM_NOT_EVALUATED : 0u);
             out[c * 64u + lane] = (uint16_t)e;                           // one 128-byte row
-            const uint32_t k = e & NHDFIT_HEADROOM_COUNT_MASK;
-            if (k) { atomicAdd(&s_tot[0], (unsigned long long)k); atomicMax(&s_tot[2], (unsigned long long)k); }
-            const uint64_t room = __ballot(k != 0u), sat = __ballot(k != 0u && k >= a.cap), stp = __ballot((e & NHDFIT_HEADROOM_STOPPED) != 0u);
-            if (lane == 0u) {
-                s_tot[1] += (unsigned long long)popc64(room); s_tot[3] += (unsigned long long)popc64(sat);
-                s_tot[4] += (unsigned long long)popc64(stp); s_tot[5] += (unsigned long long)popc64(off_word);
-            }
+            HeadroomTally{s_tot}.chunk(e, a.cap, off_word, lane);
         }
         __syncthreads();                                                 // (everybody has read the ticket; the entries are wavefront 0's to clear)
     }
     __syncthreads();
-    if (tid < 6u && s_tot[tid]) {                                        // one atomic per (block, template, field)
-        HeadroomSum* q = a.sum + tpl;
-        const unsigned long long v = s_tot[tid];
-        if (tid == 0u) atomicAdd(&q->replicas, v);
-        else if (tid == 1u) atomicAdd(&q->nodes_with_room, (uint32_t)v);
-        else if (tid == 2u) atomicMax(&q->max_on_one_node, (uint32_t)v);
-        else if (tid == 3u) atomicAdd(&q->saturated, (uint32_t)v);
-        else if (tid == 4u) atomicAdd(&q->stopped, (uint32_t)v);
-        else atomicAdd(&q->not_evaluated, (uint32_t)v);
-    }
+    HeadroomTally{s_tot}.flush<false>(a.sum + tpl, tid);
 }

@@ -1,5 +1,5 @@
 // limit_kernel.h - nhdfit_headroom_limits on the device: the stage that ends each node's headroom run (k_limit_stage).
-// Device code of libnhdfit.so; included by nhdfit.hip inside its anonymous namespace, behind explain_core.h and
+// Device code of libnhdfit.so; included by nhdfit.hip inside its anonymous namespace, behind explain_kernel.h and
 // headroom_kernel.h.  gfx950 only.
 //
 // limit(node, template) = explain_stage (explain_core.h) of the template on the node in the state in which its run ended,
@@ -14,7 +14,7 @@
 //   The view is 640 bytes and differs per (template, node), so it cannot be prepared once per call as k_explain_views does: it
 //   lives in LDS, a slot per lane, padded to 648 bytes (162 dwords: the lanes' equal fields fall into different banks) - 41 KB
 //   per 64-lane block, three blocks per CU.  Nothing of it is in private memory.
-//   Counting as k_explain: one ballot per stage, the wavefronts' counts meet in LDS, one atomicAdd per (block, template, stage).
+//   Counting is k_explain's (stage_histogram, explain_kernel.h): one atomicAdd per (block, template, stage).
 //   The stage matrix is written only when the caller asked for it.
 // The loops are explain_stage's (bounded by U^G assignments and the NIC odometer); no spin wait, no hand-off between blocks.
 constexpr size_t kHeadroomSlabBytes = 64u << 20;  // device memory for the final states of one slab of templates (208 bytes per pair:
@@ -39,7 +39,7 @@ __global__ __launch_bounds__(kLimitThreads) void k_limit_stage(LimitArgs a) {
     __shared__ LimitView s_view[kLimitThreads];
     __shared__ uint32_t s_cnt[kLimitThreads / 64][NHDFIT_STAGES];
     __shared__ nhdfit_req s_req;                                       // (its fields reach the lanes as VGPRs, as in k_explain)
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t tid = threadIdx.x;
     const uint32_t v = blockIdx.x * kLimitThreads + tid;
     const uint32_t tpl = a.tpl0 + blockIdx.y;                          // rows of reqs / counts / hist / stage; final is the slab's
     const bool live = v < a.n;
@@ -61,14 +61,5 @@ __global__ __launch_bounds__(kLimitThreads) void k_limit_stage(LimitArgs a) {
         }
         if (a.stage) a.stage[(size_t)tpl * a.n + v] = (uint8_t)st;
     }
-    for (uint32_t k = 0; k < NHDFIT_STAGES; ++k) {
-        const uint64_t m = __ballot(st == k);
-        if (lane == 0) s_cnt[wave][k] = (uint32_t)popc64(m);
-    }
-    __syncthreads();
-    if (tid < NHDFIT_STAGES) {
-        uint32_t sum = 0;
-        for (uint32_t q = 0; q < kLimitThreads / 64; ++q) sum += s_cnt[q][tid];
-        if (sum) atomicAdd(&a.hist[(size_t)tpl * NHDFIT_STAGES + tid], sum);
-    }
+    stage_histogram<kLimitThreads / 64>(s_cnt, st, a.hist, tpl, tid);
 }

@@ -37,6 +37,7 @@
 #include "explain_core.h"
 #include "dict_stream.h"
 #include "host_streams.h"
+#include "headroom_merge.h"
 
 using namespace nhdfit;
 
@@ -111,10 +112,15 @@ struct Rccl {
 };
 Rccl g_rccl;
 
+// The two buffer types own their memory: a context's buffers go with the context (nhdfit_destroy names none of them).
 template <class T>
 struct DevBuf {
     T* p = nullptr;
     size_t cap = 0;   // elements
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { release(); }
     hipError_t reserve(size_t n) {
         if (n <= cap) return hipSuccess;
         if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
@@ -129,6 +135,10 @@ template <class T>
 struct PinBuf {                   // page-locked host staging: async copies in both directions, no bounce buffer inside the runtime
     T* p = nullptr;
     size_t cap = 0;
+    PinBuf() = default;
+    PinBuf(const PinBuf&) = delete;
+    PinBuf& operator=(const PinBuf&) = delete;
+    ~PinBuf() { release(); }
     hipError_t reserve(size_t n) {
         if (n <= cap) return hipSuccess;
         if (p) { (void)hipHostFree(p); p = nullptr; cap = 0; }
@@ -138,6 +148,9 @@ struct PinBuf {                   // page-locked host staging: async copies in b
     }
     void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
 };
+static_assert(!std::is_copy_constructible<DevBuf<int>>::value && !std::is_copy_assignable<DevBuf<int>>::value &&
+              !std::is_copy_constructible<PinBuf<int>>::value && !std::is_copy_assignable<PinBuf<int>>::value,
+              "a buffer is freed once, by its one owner");
 
 constexpr int kEventRing = 256;
 constexpr int kBufs = 8;          // buffer sets: step s owns set s % kBufs from its digest (one launch before its fit)
@@ -155,6 +168,19 @@ struct Pipe {                            // one software pipeline of steps: its 
     DevBuf<unsigned long long> shape_keys[kBufs]; DevBuf<uint32_t> shape_res[kBufs]; DevBuf<int32_t> shape_slot[kBufs];   // mapping dedup tables
     DevBuf<uint32_t> shape_list[kBufs];  // distinct shapes per tile
     DevBuf<uint32_t> dig_count;          // [tiles] arrival counters of the digest blocks that share a tile's signature rows (zero between launches)
+};
+
+// Buffers of the query entries - nhdfit_explain / _big (explain_kernel.h), nhdfit_headroom (headroom_kernel.h), _limits
+// (limit_kernel.h), _general (wide_room_kernel.h).  One set for all of them: a query waits for its own results before it returns.
+struct QueryBufs {
+    DevBuf<nhdfit_req> reqs; DevBuf<nhdfit_big_req> big_reqs;   // the call's requests, by record type
+    DevBuf<uint64_t> cand;                                       // [chunks] the call's candidate mask
+    DevBuf<uint32_t> hist;                                       // [P][NHDFIT_STAGES] nodes per stage: explain's counts, the limits' histogram
+    DevBuf<uint8_t> stage;                                       // [P][n] the stage matrix of either
+    DevBuf<nhdfit_wide_node> views; DevBuf<int32_t> slot; DevBuf<uint32_t> flags;   // explain: every node as the general path reads it
+    DevBuf<uint32_t> tickets; DevBuf<HeadroomSum> sum; DevBuf<uint16_t> counts;      // headroom: ticket counters, summary records, entries
+    DevBuf<HeadroomFinal> final;                                 // limits: the runs' final states, a slab of templates at a time
+    DevBuf<uint32_t> wide_tickets;                               // general: the wide launch's ticket counters, and behind them its flag words
 };
 
 }  // namespace
@@ -273,15 +299,7 @@ struct nhdfit_ctx {
     DevBuf<nhdfit_big_req> big_reqs; DevBuf<unsigned long long> big_score; DevBuf<nhdfit_big_mapping> big_maps;
     DevBuf<uint32_t> big_flags; DevBuf<nhdfit_big_placement> big_place; DevBuf<uint64_t> big_cand; DevBuf<int32_t> big_scratch;
     uint32_t wide_max_numa = 0;                            // most sockets among the wide records (sizes a big request's set tables)
-    // nhdfit_explain / nhdfit_explain_big (explain_kernel.h): buffers of their own - an explanation leaves the staged batch alone
-    DevBuf<nhdfit_wide_node> ex_views; DevBuf<int32_t> ex_slot; DevBuf<nhdfit_req> ex_reqs; DevBuf<nhdfit_big_req> ex_big_reqs;
-    DevBuf<uint32_t> ex_counts, ex_flags; DevBuf<uint64_t> ex_cand; DevBuf<uint8_t> ex_stage;
-    // nhdfit_headroom (headroom_kernel.h): buffers of its own as well
-    DevBuf<nhdfit_req> hr_reqs; DevBuf<uint32_t> hr_tickets; DevBuf<HeadroomSum> hr_sum; DevBuf<uint16_t> hr_counts; DevBuf<uint64_t> hr_cand;
-    // nhdfit_headroom_limits (limit_kernel.h): the runs' final states, a slab of templates at a time, and the stage histogram / matrix
-    DevBuf<HeadroomFinal> hr_final; DevBuf<uint32_t> hr_hist; DevBuf<uint8_t> hr_stage;
-    // nhdfit_headroom_general (wide_room_kernel.h): the wide launch's ticket counters, and behind them its flag words
-    DevBuf<uint32_t> hr_wide_tickets;
+    QueryBufs q;                         // nhdfit_explain* / nhdfit_headroom*: buffers of their own - a query leaves the staged batch alone
     int wide_slot(uint32_t node) const {
         auto it = std::lower_bound(wide_index.begin(), wide_index.end(), node);
         return it != wide_index.end() && *it == node ? (int)(it - wide_index.begin()) : -1;
@@ -567,29 +585,11 @@ void nhdfit_destroy(nhdfit_ctx* c) {
     (void)hipSetDevice(c->dev);
     (void)hipDeviceSynchronize();
     if (c->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(c->comm);
-    c->p0.release(); c->p1.release(); c->p2.release(); c->p3.release(); c->p4.release(); c->det.release();
-    c->origin.release(); c->deltas.release(); c->delta_run.release(); c->delta_status.release();
-    c->wide.release(); c->wide_share.release(); c->wide_scratch.release(); c->wide_flags.release(); c->wide_place.release();
-    c->big_reqs.release(); c->big_score.release(); c->big_maps.release(); c->big_flags.release(); c->big_place.release();
-    c->big_cand.release(); c->big_scratch.release();
-    c->ex_views.release(); c->ex_slot.release(); c->ex_reqs.release(); c->ex_big_reqs.release(); c->ex_counts.release(); c->ex_flags.release();
-    c->ex_cand.release(); c->ex_stage.release();
-    c->hr_reqs.release(); c->hr_tickets.release(); c->hr_sum.release(); c->hr_counts.release(); c->hr_cand.release(); c->hr_wide_tickets.release();
-    if (c->find_host) (void)hipHostFree(c->find_host);
+    if (c->find_host) (void)hipHostFree(c->find_host);              // the hipHostMalloc blocks that are no PinBuf
     if (c->commit_host) (void)hipHostFree(c->commit_host);
-    c->commit_host = nullptr;
     if (c->findn_host) (void)hipHostFree(c->findn_host);
-    c->findn_host = nullptr; c->findn_cap = 0; c->findn_sync.release();
-    c->find_host = nullptr; c->find_sync.release(); c->find_red.release();
-    c->pin_order.release(); c->pin_reqs.release(); c->pin_wcls.release(); c->pin_score.release(); c->pin_maps.release(); c->pin_items.release();
-    c->caps.release(); c->sig_off.release(); c->pool_off.release(); c->pool_glimit.release(); c->cc.release(); c->sig_flat.release(); c->sig_flat2.release();
-    c->reqs.release(); c->bitmap.release(); c->rows_t.release(); c->cand.release(); c->tile_wcls.release(); c->items.release(); c->xkeys.release(); c->xids.release(); c->xcls.release(); c->xnx.release(); c->sig_use.release(); for (auto& r : c->rec) r.release(); c->role_clock.release(); c->asc.release(); c->choose_tab.release(); c->st_info.release(); c->st_next.release(); c->st_asc.release(); c->group_sets.release();
-    c->nogpu.release(); c->taken.release(); c->tile_masks.release(); c->touched.release(); c->gl_tiles.release(); c->seq_counters.release(); c->undo.release(); c->seq_out.release(); c->seq_place.release(); c->order.release(); c->seq_queue.release(); c->seq_ctrl.release(); c->seq_mat.release(); c->seq_flags.release(); c->seq_ent.release(); c->sig_keys.release(); c->sig_ids.release();
     for (Pipe& p : c->pipe) {
-        p.nm.release(); p.dig_count.release();
         for (int b = 0; b < kBufs; ++b) {
-            p.hdr[b].release(); p.tabs[b].release(); p.score[b].release(); p.maps[b].release();
-            p.shape_keys[b].release(); p.shape_res[b].release(); p.shape_slot[b].release(); p.shape_list[b].release();
             if (p.ev_fit[b]) (void)hipEventDestroy(p.ev_fit[b]);
             if (p.ev_red[b]) (void)hipEventDestroy(p.ev_red[b]);
         }
@@ -599,7 +599,7 @@ void nhdfit_destroy(nhdfit_ctx* c) {
         for (auto& x : q)
             if (x) (void)hipEventDestroy(x);
     c->streams.destroy();
-    delete c;
+    delete c;                    // every DevBuf / PinBuf frees itself: the device is current, nothing is in flight
 }
 
 int nhdfit_set_dictionary(nhdfit_ctx* c, uint32_t max_cores_per_numa, uint32_t max_gpus_per_numa,
@@ -2856,6 +2856,22 @@ int nhdfit_group_find(nhdfit_group* g, const nhdfit_req* reqs, uint32_t P, doubl
 // ---- explain: the stage at which each node turned each pod away (explain_kernel.h) --------------------------------------------------
 }  // extern "C"
 namespace {
+// What every query starts with: the mirror as the last call left it (steps in flight are drained, their results stay fetchable), then
+// the call's requests and - where the mirror has nodes - its optional candidate mask on their way to the device.
+template <class R>
+int stage_query(nhdfit_ctx* c, DevBuf<R>& dreqs, const R* reqs, uint32_t P, const uint64_t* cand) {
+    HIPCHK(c, hipSetDevice(c->dev));
+    TRY(sync_all(c));
+    HIPCHK(c, dreqs.reserve(P));
+    HIPCHK(c, hipMemcpyAsync(dreqs.p, reqs, (size_t)P * sizeof *reqs, hipMemcpyHostToDevice, c->streams.use(0)));
+    if (cand && c->n) {
+        const size_t chunks = (c->n + 63) / 64;
+        HIPCHK(c, c->q.cand.reserve(chunks));
+        HIPCHK(c, hipMemcpyAsync(c->q.cand.p, cand, chunks * sizeof(uint64_t), hipMemcpyHostToDevice, c->streams.use(0)));
+    }
+    return NHDFIT_OK;
+}
+
 template <class R>
 int explain_run(nhdfit_ctx* c, DevBuf<R>& dreqs, const R* reqs, uint32_t P, double now, const uint64_t* cand, uint32_t* counts_out,
                 uint8_t* stage_out, uint32_t budget) {
@@ -2863,58 +2879,67 @@ int explain_run(nhdfit_ctx* c, DevBuf<R>& dreqs, const R* reqs, uint32_t P, doub
     if (!reqs || !P || !counts_out) return fail(c, NHDFIT_E_INVAL, "explain: requests and counts_out are required");
     if ((P + kExplainPods - 1) / kExplainPods > 65535u) return fail(c, NHDFIT_E_LIMIT, "%u requests in one explain call (<= %u)", P, 65535u * kExplainPods);
     if (c->n && !c->ncls) return fail(c, NHDFIT_E_STATE, "set the dictionary first (nhdfit_set_dictionary: the NIC capacity classes)");
-    HIPCHK(c, hipSetDevice(c->dev));
-    TRY(sync_all(c));             // (the mirror as the last call left it)
+    TRY(stage_query(c, dreqs, reqs, P, cand));
+    QueryBufs& q = c->q;
     const uint32_t n = c->n;
-    const size_t chunks = (n + 63) / 64;
-    HIPCHK(c, dreqs.reserve(P));
-    HIPCHK(c, c->ex_counts.reserve((size_t)P * NHDFIT_STAGES));
-    HIPCHK(c, c->ex_flags.reserve(1));
-    HIPCHK(c, hipMemcpyAsync(dreqs.p, reqs, (size_t)P * sizeof *reqs, hipMemcpyHostToDevice, c->streams.use(0)));
-    HIPCHK(c, hipMemsetAsync(c->ex_counts.p, 0, (size_t)P * NHDFIT_STAGES * sizeof(uint32_t), c->streams.use(0)));
-    HIPCHK(c, hipMemsetAsync(c->ex_flags.p, 0, sizeof(uint32_t), c->streams.use(0)));
+    HIPCHK(c, q.hist.reserve((size_t)P * NHDFIT_STAGES));
+    HIPCHK(c, q.flags.reserve(1));
+    HIPCHK(c, hipMemsetAsync(q.hist.p, 0, (size_t)P * NHDFIT_STAGES * sizeof(uint32_t), c->streams.use(0)));
+    HIPCHK(c, hipMemsetAsync(q.flags.p, 0, sizeof(uint32_t), c->streams.use(0)));
     if (n) {
-        HIPCHK(c, c->ex_views.reserve(n));
-        HIPCHK(c, c->ex_slot.reserve(n));
-        if (stage_out) HIPCHK(c, c->ex_stage.reserve((size_t)P * n));
-        if (cand) {
-            HIPCHK(c, c->ex_cand.reserve(chunks));
-            HIPCHK(c, hipMemcpyAsync(c->ex_cand.p, cand, chunks * sizeof(uint64_t), hipMemcpyHostToDevice, c->streams.use(0)));
-        }
+        HIPCHK(c, q.views.reserve(n));
+        HIPCHK(c, q.slot.reserve(n));
+        if (stage_out) HIPCHK(c, q.stage.reserve((size_t)P * n));
         ExplainViewArgs va;
         memset(&va, 0, sizeof va);
         va.p0 = c->p0.p; va.p1 = c->p1.p; va.p2 = c->p2.p; va.p3 = c->p3.p; va.p4 = c->p4.p; va.det = c->det.p; va.n = n;
-        va.wide = c->wide.p; va.n_wide = c->n_wide; va.views = c->ex_views.p; va.slot = c->ex_slot.p;
+        va.wide = c->wide.p; va.n_wide = c->n_wide; va.views = q.views.p; va.slot = q.slot.p;
         hipLaunchKernelGGL(k_explain_views, dim3((n + kExplainThreads - 1) / kExplainThreads), dim3(kExplainThreads), 0, c->streams.use(0), va);
         HIPCHK(c, hipGetLastError());
         ExplainArgs<R> ea;
         memset(&ea, 0, sizeof ea);
-        ea.views = c->ex_views.p; ea.slot = c->ex_slot.p; ea.n = n; ea.wide = c->wide.p; ea.share = c->sharing ? c->wide_share.p : nullptr;
-        ea.reqs = dreqs.p; ea.P = P; ea.caps = c->caps.p; ea.busy_from = busy_threshold(now); ea.cand = cand ? c->ex_cand.p : nullptr;
-        ea.budget = budget; ea.counts = c->ex_counts.p; ea.stage = stage_out ? c->ex_stage.p : nullptr; ea.flags = c->ex_flags.p;
+        ea.views = q.views.p; ea.slot = q.slot.p; ea.n = n; ea.wide = c->wide.p; ea.share = c->sharing ? c->wide_share.p : nullptr;
+        ea.reqs = dreqs.p; ea.P = P; ea.caps = c->caps.p; ea.busy_from = busy_threshold(now); ea.cand = cand ? q.cand.p : nullptr;
+        ea.budget = budget; ea.counts = q.hist.p; ea.stage = stage_out ? q.stage.p : nullptr; ea.flags = q.flags.p;
         hipLaunchKernelGGL(k_explain<R>, dim3((n + kExplainThreads - 1) / kExplainThreads, (P + kExplainPods - 1) / kExplainPods), dim3(kExplainThreads), 0,
                c->streams.use(0), ea);
         HIPCHK(c, hipGetLastError());
-        if (stage_out) HIPCHK(c, hipMemcpyAsync(stage_out, c->ex_stage.p, (size_t)P * n, hipMemcpyDeviceToHost, c->streams.use(0)));
+        if (stage_out) HIPCHK(c, hipMemcpyAsync(stage_out, q.stage.p, (size_t)P * n, hipMemcpyDeviceToHost, c->streams.use(0)));
     }
     uint32_t fl = 0;
-    HIPCHK(c, hipMemcpyAsync(counts_out, c->ex_counts.p, (size_t)P * NHDFIT_STAGES * sizeof(uint32_t), hipMemcpyDeviceToHost, c->streams.use(0)));
-    HIPCHK(c, hipMemcpyAsync(&fl, c->ex_flags.p, sizeof fl, hipMemcpyDeviceToHost, c->streams.use(0)));
+    HIPCHK(c, hipMemcpyAsync(counts_out, q.hist.p, (size_t)P * NHDFIT_STAGES * sizeof(uint32_t), hipMemcpyDeviceToHost, c->streams.use(0)));
+    HIPCHK(c, hipMemcpyAsync(&fl, q.flags.p, sizeof fl, hipMemcpyDeviceToHost, c->streams.use(0)));
     HIPCHK(c, c->streams.wait(0));
     if (fl) return fail(c, NHDFIT_E_LIMIT, "a big request's NIC stage ran out of search budget on some node (%u steps per NIC question, pod and node)", budget);
     return NHDFIT_OK;
+}
+
+// A query over every shard of a group: call(shard's context, k) answers for shard k and merges its part into the group's answer;
+// the first shard that fails ends the call, its error text becomes the group's.
+template <class Call>
+int group_each(nhdfit_group* g, Call call) {
+    for (size_t k = 0; k < g->ctx.size(); ++k) {
+        const int rc = call(g->ctx[k], k);
+        if (rc) { g->err = g->ctx[k]->err; return rc; }
+    }
+    return NHDFIT_OK;
+}
+// (the k-th of a group call's optional per-shard pointers)
+template <class T> T* shard_ptr(T* const* list, size_t k) { return list ? list[k] : nullptr; }
+void add_counts(uint32_t* total, const std::vector<uint32_t>& part) {
+    for (size_t j = 0; j < part.size(); ++j) total[j] += part[j];
 }
 }  // namespace
 extern "C" {
 
 int nhdfit_explain(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, double now, const uint64_t* cand, uint32_t* counts_out, uint8_t* stage_out) {
     if (!c) return NHDFIT_E_INVAL;
-    return explain_run(c, c->ex_reqs, reqs, P, now, cand, counts_out, stage_out, 0u);
+    return explain_run(c, c->q.reqs, reqs, P, now, cand, counts_out, stage_out, 0u);
 }
 
 int nhdfit_explain_big(nhdfit_ctx* c, const nhdfit_big_req* reqs, uint32_t P, double now, const uint64_t* cand, uint32_t* counts_out, uint8_t* stage_out) {
     if (!c) return NHDFIT_E_INVAL;
-    return explain_run(c, c->ex_big_reqs, reqs, P, now, cand, counts_out, stage_out, (uint32_t)NHDFIT_BIG_NIC_BUDGET);
+    return explain_run(c, c->q.big_reqs, reqs, P, now, cand, counts_out, stage_out, (uint32_t)NHDFIT_BIG_NIC_BUDGET);
 }
 
 int nhdfit_group_explain(nhdfit_group* g, const nhdfit_req* reqs, uint32_t P, double now, const uint64_t* const* cand, uint32_t* counts_out,
@@ -2922,13 +2947,11 @@ int nhdfit_group_explain(nhdfit_group* g, const nhdfit_req* reqs, uint32_t P, do
     if (!g || !reqs || !P || !counts_out) return NHDFIT_E_INVAL;
     std::vector<uint32_t> part((size_t)P * NHDFIT_STAGES);
     memset(counts_out, 0, part.size() * sizeof(uint32_t));
-    for (size_t k = 0; k < g->ctx.size(); ++k) {
-        nhdfit_ctx* c = g->ctx[k];
-        const int rc = nhdfit_explain(c, reqs, P, now, cand ? cand[k] : nullptr, part.data(), stage_out ? stage_out[k] : nullptr);
-        if (rc) { g->err = c->err; return rc; }
-        for (size_t j = 0; j < part.size(); ++j) counts_out[j] += part[j];
-    }
-    return NHDFIT_OK;
+    return group_each(g, [&](nhdfit_ctx* c, size_t k) {
+        const int rc = nhdfit_explain(c, reqs, P, now, shard_ptr(cand, k), part.data(), shard_ptr(stage_out, k));
+        if (!rc) add_counts(counts_out, part);
+        return rc;
+    });
 }
 
 // ---- headroom: how many more replicas of a pod template each node can take (headroom_kernel.h) ---------------------------------------
@@ -2954,42 +2977,36 @@ int headroom_run(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, const uint64
     // (a stream of more than kDictLdsWords words is read where it lies, headroom_kernel.h; flat_words == 0: it does not fit 16-bit offsets)
     if (!c->flat_words || c->nsig > kLoneMaxSigs)
         return fail(c, NHDFIT_E_LIMIT, "headroom: the dictionary has %u NIC signatures (<= %u, in a stream of at most 65535 words)", c->nsig, kLoneMaxSigs);
-    HIPCHK(c, hipSetDevice(c->dev));
-    TRY(sync_all(c));             // (the mirror as the last call left it; steps in flight are drained, their results stay fetchable)
+    QueryBufs& q = c->q;
+    TRY(stage_query(c, q.reqs, reqs, P, cand));
     const uint32_t chunks = (n + 63) / 64;
     const size_t pitch = (size_t)chunks * 64;
-    HIPCHK(c, c->hr_reqs.reserve(P));
-    HIPCHK(c, c->hr_tickets.reserve(P));
-    HIPCHK(c, c->hr_sum.reserve(P));
-    HIPCHK(c, c->hr_counts.reserve((size_t)P * pitch));
+    HIPCHK(c, q.tickets.reserve(P));
+    HIPCHK(c, q.sum.reserve(P));
+    HIPCHK(c, q.counts.reserve((size_t)P * pitch));
     // the final states of one slab of templates: as many as the budget holds, one at the least (every loop below is bounded by P)
     const uint32_t slab = limits_out ? (uint32_t)std::min<size_t>(P, std::max<size_t>(1, slab_bytes / (pitch * sizeof(HeadroomFinal)))) : P;
     if (limits_out) {
-        HIPCHK(c, c->hr_final.reserve((size_t)slab * pitch));
-        HIPCHK(c, c->hr_hist.reserve((size_t)P * NHDFIT_STAGES));
-        if (stage_out) HIPCHK(c, c->hr_stage.reserve((size_t)P * n));
-        HIPCHK(c, hipMemsetAsync(c->hr_hist.p, 0, (size_t)P * NHDFIT_STAGES * sizeof(uint32_t), c->streams.use(0)));
+        HIPCHK(c, q.final.reserve((size_t)slab * pitch));
+        HIPCHK(c, q.hist.reserve((size_t)P * NHDFIT_STAGES));
+        if (stage_out) HIPCHK(c, q.stage.reserve((size_t)P * n));
+        HIPCHK(c, hipMemsetAsync(q.hist.p, 0, (size_t)P * NHDFIT_STAGES * sizeof(uint32_t), c->streams.use(0)));
     }
-    HIPCHK(c, hipMemcpyAsync(c->hr_reqs.p, reqs, (size_t)P * sizeof *reqs, hipMemcpyHostToDevice, c->streams.use(0)));
-    HIPCHK(c, hipMemsetAsync(c->hr_tickets.p, 0, (size_t)P * sizeof(uint32_t), c->streams.use(0)));
-    HIPCHK(c, hipMemsetAsync(c->hr_sum.p, 0, (size_t)P * sizeof(HeadroomSum), c->streams.use(0)));
-    if (cand) {
-        HIPCHK(c, c->hr_cand.reserve(chunks));
-        HIPCHK(c, hipMemcpyAsync(c->hr_cand.p, cand, (size_t)chunks * sizeof(uint64_t), hipMemcpyHostToDevice, c->streams.use(0)));
-    }
+    HIPCHK(c, hipMemsetAsync(q.tickets.p, 0, (size_t)P * sizeof(uint32_t), c->streams.use(0)));
+    HIPCHK(c, hipMemsetAsync(q.sum.p, 0, (size_t)P * sizeof(HeadroomSum), c->streams.use(0)));
     HeadroomArgs a;
     memset(&a, 0, sizeof a);
     a.p0 = c->p0.p; a.p1 = c->p1.p; a.p2 = c->p2.p; a.p3 = c->p3.p; a.p4 = c->p4.p; a.det = c->det.p; a.n = n;
     a.wide = c->wide.p; a.n_wide = c->n_wide;
-    a.reqs = c->hr_reqs.p;
+    a.reqs = q.reqs.p;
     a.d = DictView{c->caps.p, c->ncls, c->group_sets.p, SigDict{c->sig_off.p, c->pool_off.p, c->pool_glimit.p, c->cc.p, c->nsig}, c->sig_flat.p, c->flat_words, nullptr, 0};
     a.nsig = c->nsig; a.fc_dim = c->max_cores + 1; a.fg_dim = c->max_gpus + 1; a.ngs = c->ngs;
     const ShapeArgs sh = make_shape_args(c, c->pipe[0], 0);
     a.mt = MapTables{sh.asc, sh.choose_tab, sh.st};
     a.sigs = sig_table(c); a.ncls = c->ncls;
-    a.cand = cand ? c->hr_cand.p : nullptr;
+    a.cand = cand ? q.cand.p : nullptr;
     a.chunks = chunks; a.cap = max_per_node;
-    a.tickets = c->hr_tickets.p; a.counts = c->hr_counts.p; a.sum = c->hr_sum.p;
+    a.tickets = q.tickets.p; a.counts = q.counts.p; a.sum = q.sum.p;
     a.all_generic = a.mt.choose_tab && a.mt.st.info ? 0u : 1u;
     std::vector<uint32_t> form(P);
     for (uint32_t p = 0; p < P; ++p)
@@ -3000,8 +3017,8 @@ int headroom_run(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, const uint64
         bool any_wave = false, any_g4 = false;
         for (uint32_t p = t0; p < t0 + S; ++p) (form[p] == NHDFIT_HEADROOM_FORM_GENERIC ? any_g4 : any_wave) = true;
         // the kernel indexes by blockIdx.y: it is handed the slab's rows; only `final` is the slab's own
-        a.reqs = c->hr_reqs.p + t0; a.tickets = c->hr_tickets.p + t0; a.sum = c->hr_sum.p + t0; a.counts = c->hr_counts.p + (size_t)t0 * pitch;
-        a.final = limits_out ? c->hr_final.p : nullptr;
+        a.reqs = q.reqs.p + t0; a.tickets = q.tickets.p + t0; a.sum = q.sum.p + t0; a.counts = q.counts.p + (size_t)t0 * pitch;
+        a.final = limits_out ? q.final.p : nullptr;
         // blocks per template: the chip's block slots shared out among the templates, a chunk per block at the least
         const uint32_t nb = std::max(1u, std::min(chunks, (slots + S - 1) / S));
         if (any_wave) hipLaunchKernelGGL(k_headroom<false>, dim3(nb, S), dim3(kHeadroomBlock), kHeadroomLds, c->streams.use(0), a);
@@ -3012,41 +3029,41 @@ int headroom_run(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, const uint64
         LimitArgs la;
         memset(&la, 0, sizeof la);
         la.p0 = a.p0; la.p1 = a.p1; la.p2 = a.p2; la.p3 = a.p3; la.p4 = a.p4; la.det = a.det; la.n = n;
-        la.reqs = c->hr_reqs.p; la.caps = c->caps.p; la.cand = a.cand;
-        la.counts = c->hr_counts.p; la.pitch = pitch; la.final = c->hr_final.p; la.tpl0 = t0;
-        la.hist = c->hr_hist.p; la.stage = stage_out ? c->hr_stage.p : nullptr;
+        la.reqs = q.reqs.p; la.caps = c->caps.p; la.cand = a.cand;
+        la.counts = q.counts.p; la.pitch = pitch; la.final = q.final.p; la.tpl0 = t0;
+        la.hist = q.hist.p; la.stage = stage_out ? q.stage.p : nullptr;
         hipLaunchKernelGGL(k_limit_stage, dim3((n + kLimitThreads - 1) / kLimitThreads, S), dim3(kLimitThreads), 0, c->streams.use(0), la);
         HIPCHK(c, hipGetLastError());
     }
     if (limits_out) {
-        HIPCHK(c, hipMemcpyAsync(limits_out, c->hr_hist.p, (size_t)P * NHDFIT_STAGES * sizeof(uint32_t), hipMemcpyDeviceToHost, c->streams.use(0)));
-        if (stage_out) HIPCHK(c, hipMemcpyAsync(stage_out, c->hr_stage.p, (size_t)P * n, hipMemcpyDeviceToHost, c->streams.use(0)));
+        HIPCHK(c, hipMemcpyAsync(limits_out, q.hist.p, (size_t)P * NHDFIT_STAGES * sizeof(uint32_t), hipMemcpyDeviceToHost, c->streams.use(0)));
+        if (stage_out) HIPCHK(c, hipMemcpyAsync(stage_out, q.stage.p, (size_t)P * n, hipMemcpyDeviceToHost, c->streams.use(0)));
     }
     const bool wide_ran = general && !limits_out && c->n_wide != 0;
     uint32_t wide_flags[4] = {0, 0, 0, 0};
     if (wide_ran) {
         const uint32_t wchunks = (c->n_wide + 63) / 64;
-        HIPCHK(c, c->hr_wide_tickets.reserve((size_t)P + 4));
-        HIPCHK(c, hipMemsetAsync(c->hr_wide_tickets.p, 0, ((size_t)P + 4) * sizeof(uint32_t), c->streams.use(0)));
+        HIPCHK(c, q.wide_tickets.reserve((size_t)P + 4));
+        HIPCHK(c, hipMemsetAsync(q.wide_tickets.p, 0, ((size_t)P + 4) * sizeof(uint32_t), c->streams.use(0)));
         WideRoomArgs wa;
         memset(&wa, 0, sizeof wa);
         wa.wide = c->wide.p; wa.n_wide = c->n_wide; wa.share = c->sharing ? c->wide_share.p : nullptr;
-        wa.reqs = c->hr_reqs.p; wa.caps = c->caps.p; wa.ncls = c->ncls;
-        wa.cand = cand ? c->hr_cand.p : nullptr;
+        wa.reqs = q.reqs.p; wa.caps = c->caps.p; wa.ncls = c->ncls;
+        wa.cand = cand ? q.cand.p : nullptr;
         wa.n = n; wa.wchunks = wchunks; wa.cap = max_per_node; wa.pitch = pitch;
-        wa.tickets = c->hr_wide_tickets.p; wa.counts = c->hr_counts.p; wa.sum = c->hr_sum.p; wa.flags = c->hr_wide_tickets.p + P;
+        wa.tickets = q.wide_tickets.p; wa.counts = q.counts.p; wa.sum = q.sum.p; wa.flags = q.wide_tickets.p + P;
         // blocks (of one wavefront, three to a CU: 41 KB of LDS each) per template: the chip's slots shared out among the templates, at most
         // one per record - a record's run is the unit of work, and the runs differ by orders of magnitude
         const uint32_t wslots = 3u * (uint32_t)c->prop.multiProcessorCount;
         const uint32_t wb = std::max(1u, std::min(wchunks, (wslots + P - 1) / P));
         hipLaunchKernelGGL(k_wide_room, dim3(wb, P), dim3(kWideRoomBlock), 0, c->streams.use(0), wa);
         HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(wide_flags, c->hr_wide_tickets.p + P, sizeof wide_flags, hipMemcpyDeviceToHost, c->streams.use(0)));
+        HIPCHK(c, hipMemcpyAsync(wide_flags, q.wide_tickets.p + P, sizeof wide_flags, hipMemcpyDeviceToHost, c->streams.use(0)));
     }
     static_assert(sizeof(HeadroomSum) == sizeof(nhdfit_headroom_sum), "copied out as it is");
-    HIPCHK(c, hipMemcpyAsync(sum_out, c->hr_sum.p, (size_t)P * sizeof *sum_out, hipMemcpyDeviceToHost, c->streams.use(0)));
+    HIPCHK(c, hipMemcpyAsync(sum_out, q.sum.p, (size_t)P * sizeof *sum_out, hipMemcpyDeviceToHost, c->streams.use(0)));
     if (counts_out)
-        HIPCHK(c, hipMemcpy2DAsync(counts_out, (size_t)n * sizeof(uint16_t), c->hr_counts.p, pitch * sizeof(uint16_t), (size_t)n * sizeof(uint16_t), P,
+        HIPCHK(c, hipMemcpy2DAsync(counts_out, (size_t)n * sizeof(uint16_t), q.counts.p, pitch * sizeof(uint16_t), (size_t)n * sizeof(uint16_t), P,
                                    hipMemcpyDeviceToHost, c->streams.use(0)));
     HIPCHK(c, c->streams.wait(0));
     if (wide_flags[0]) {                                                 // (never expected) no half-corrected figures go out with the error
@@ -3072,13 +3089,6 @@ int nhdfit_headroom(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, const uin
     return headroom_run(c, reqs, P, cand, max_per_node, sum_out, counts_out, nullptr, nullptr, 0);
 }
 
-int nhdfit_headroom_limits(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, const uint64_t* cand, uint32_t max_per_node, nhdfit_headroom_sum* sum_out,
-                           uint16_t* counts_out, uint32_t* limits_out, uint8_t* stage_out) {
-    if (!c) return NHDFIT_E_INVAL;
-    if (!limits_out) return fail(c, NHDFIT_E_INVAL, "headroom limits: limits_out is required");
-    return headroom_run(c, reqs, P, cand, max_per_node, sum_out, counts_out, limits_out, stage_out, kHeadroomSlabBytes);
-}
-
 // Not part of include/nhdfit.h: nhdfit_headroom_limits with the budget of final states as an argument (0: the default), so that a test
 // can make a few templates take several slabs.  The answers do not depend on it.
 int nhdfit_headroom_limits_slab(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, const uint64_t* cand, uint32_t max_per_node, nhdfit_headroom_sum* sum_out,
@@ -3088,35 +3098,22 @@ int nhdfit_headroom_limits_slab(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t 
     return headroom_run(c, reqs, P, cand, max_per_node, sum_out, counts_out, limits_out, stage_out, slab_bytes ? (size_t)slab_bytes : kHeadroomSlabBytes);
 }
 
-}  // extern "C"
-namespace {
-// a shard's summary records into the group's (nhdfit_group_headroom, nhdfit_group_headroom_limits)
-void add_headroom_sums(nhdfit_headroom_sum* sum_out, const nhdfit_headroom_sum* part, uint32_t P) {
-    for (uint32_t p = 0; p < P; ++p) {
-        nhdfit_headroom_sum& s = sum_out[p];
-        s.replicas += part[p].replicas; s.nodes_with_room += part[p].nodes_with_room; s.saturated += part[p].saturated;
-        s.stopped += part[p].stopped; s.not_evaluated += part[p].not_evaluated;
-        s.max_on_one_node = std::max(s.max_on_one_node, part[p].max_on_one_node);
-        // (the planes' instantiation: the larger; the wide launch's bit: whether any shard ran it)
-        s.form = std::max(s.form & 3u, part[p].form & 3u) | ((s.form | part[p].form) & NHDFIT_HEADROOM_FORM_WIDE);
-    }
+int nhdfit_headroom_limits(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, const uint64_t* cand, uint32_t max_per_node, nhdfit_headroom_sum* sum_out,
+                           uint16_t* counts_out, uint32_t* limits_out, uint8_t* stage_out) {
+    return nhdfit_headroom_limits_slab(c, reqs, P, cand, max_per_node, sum_out, counts_out, limits_out, stage_out, 0);
 }
-}  // namespace
 
-extern "C" {
-
+// The group forms: a shard's summary records go into the group's by the rule of headroom_merge.h, its histogram is added.
 int nhdfit_group_headroom(nhdfit_group* g, const nhdfit_req* reqs, uint32_t P, const uint64_t* const* cand, uint32_t max_per_node,
                           nhdfit_headroom_sum* sum_out, uint16_t* const* counts_out) {
     if (!g || !reqs || !P || !sum_out) return NHDFIT_E_INVAL;
     std::vector<nhdfit_headroom_sum> part(P);
     memset(sum_out, 0, (size_t)P * sizeof *sum_out);
-    for (size_t k = 0; k < g->ctx.size(); ++k) {
-        nhdfit_ctx* c = g->ctx[k];
-        const int rc = nhdfit_headroom(c, reqs, P, cand ? cand[k] : nullptr, max_per_node, part.data(), counts_out ? counts_out[k] : nullptr);
-        if (rc) { g->err = c->err; return rc; }
-        add_headroom_sums(sum_out, part.data(), P);
-    }
-    return NHDFIT_OK;
+    return group_each(g, [&](nhdfit_ctx* c, size_t k) {
+        const int rc = nhdfit_headroom(c, reqs, P, shard_ptr(cand, k), max_per_node, part.data(), shard_ptr(counts_out, k));
+        if (!rc) merge_headroom_sums(sum_out, part.data(), P);
+        return rc;
+    });
 }
 
 int nhdfit_group_headroom_general(nhdfit_group* g, const nhdfit_req* reqs, uint32_t P, const uint64_t* const* cand, uint32_t max_per_node,
@@ -3124,13 +3121,11 @@ int nhdfit_group_headroom_general(nhdfit_group* g, const nhdfit_req* reqs, uint3
     if (!g || !reqs || !P || !sum_out) return NHDFIT_E_INVAL;
     std::vector<nhdfit_headroom_sum> part(P);
     memset(sum_out, 0, (size_t)P * sizeof *sum_out);
-    for (size_t k = 0; k < g->ctx.size(); ++k) {
-        nhdfit_ctx* c = g->ctx[k];
-        const int rc = nhdfit_headroom_general(c, reqs, P, cand ? cand[k] : nullptr, max_per_node, part.data(), counts_out ? counts_out[k] : nullptr);
-        if (rc) { g->err = c->err; return rc; }
-        add_headroom_sums(sum_out, part.data(), P);
-    }
-    return NHDFIT_OK;
+    return group_each(g, [&](nhdfit_ctx* c, size_t k) {
+        const int rc = nhdfit_headroom_general(c, reqs, P, shard_ptr(cand, k), max_per_node, part.data(), shard_ptr(counts_out, k));
+        if (!rc) merge_headroom_sums(sum_out, part.data(), P);
+        return rc;
+    });
 }
 
 int nhdfit_group_headroom_limits(nhdfit_group* g, const nhdfit_req* reqs, uint32_t P, const uint64_t* const* cand, uint32_t max_per_node,
@@ -3140,15 +3135,12 @@ int nhdfit_group_headroom_limits(nhdfit_group* g, const nhdfit_req* reqs, uint32
     std::vector<uint32_t> hist((size_t)P * NHDFIT_STAGES);
     memset(sum_out, 0, (size_t)P * sizeof *sum_out);
     memset(limits_out, 0, hist.size() * sizeof(uint32_t));
-    for (size_t k = 0; k < g->ctx.size(); ++k) {
-        nhdfit_ctx* c = g->ctx[k];
-        const int rc = nhdfit_headroom_limits(c, reqs, P, cand ? cand[k] : nullptr, max_per_node, part.data(), counts_out ? counts_out[k] : nullptr,
-                                              hist.data(), stage_out ? stage_out[k] : nullptr);
-        if (rc) { g->err = c->err; return rc; }
-        add_headroom_sums(sum_out, part.data(), P);
-        for (size_t j = 0; j < hist.size(); ++j) limits_out[j] += hist[j];
-    }
-    return NHDFIT_OK;
+    return group_each(g, [&](nhdfit_ctx* c, size_t k) {
+        const int rc = nhdfit_headroom_limits(c, reqs, P, shard_ptr(cand, k), max_per_node, part.data(), shard_ptr(counts_out, k), hist.data(),
+                                              shard_ptr(stage_out, k));
+        if (!rc) { merge_headroom_sums(sum_out, part.data(), P); add_counts(limits_out, hist); }
+        return rc;
+    });
 }
 
 int nhdfit_get_stats(nhdfit_ctx* c, nhdfit_stats* out) {

@@ -1,6 +1,6 @@
 // wide_room_kernel.h - nhdfit_headroom_general on the device: how many more replicas of a pod template every WIDE record can take
 // (k_wide_room).  Device code of libnhdfit.so; included by nhdfit.hip inside its anonymous namespace, behind wide_kernel.h and
-// headroom_kernel.h (HeadroomSum).  gfx950 only.
+// headroom_kernel.h (HeadroomSum, HeadroomTally).  gfx950 only.
 //
 // k_headroom (headroom_kernel.h) answers for the planes and flags a candidate the mirror holds as a wide record - 3 or 4 sockets, 65..128
 // cores per socket, every node of an ENABLE_SHARING mirror - NOT_EVALUATED.  This kernel runs behind it on the same stream and answers
@@ -139,7 +139,7 @@ __global__ __launch_bounds__(kWideRoomBlock) void k_wide_room(WideRoomArgs a) {
     __shared__ __align__(16) WideRoomLds s_t;
     __shared__ double s_caps[NHDFIT_MAX_CLASSES];
     __shared__ uint32_t s_cnt[64];
-    __shared__ unsigned long long s_tot[8];                              // [0] replicas [1] nodes with room [2] max [3] saturated [4] stopped [5] evaluated here
+    __shared__ unsigned long long s_tot[8];                              // the block's partial sums (HeadroomTally)
     const uint32_t tpl = blockIdx.y, lane = threadIdx.x;
     const nhdfit_req r = a.reqs[tpl];
     if (lane < (uint32_t)NHDFIT_MAX_CLASSES) s_caps[lane] = lane < a.ncls ? a.caps[lane] : 0.0;
@@ -193,26 +193,11 @@ __global__ __launch_bounds__(kWideRoomBlock) void k_wide_room(WideRoomArgs a) {
         }
         const uint32_t e = s_cnt[lane];
         if (listed_word >> lane & 1ull) out[index] = (uint16_t)e;        // over k_headroom's NOT_EVALUATED
-        const uint32_t k = e & NHDFIT_HEADROOM_COUNT_MASK;
-        if (k) { atomicAdd(&s_tot[0], (unsigned long long)k); atomicMax(&s_tot[2], (unsigned long long)k); }
-        const uint64_t room = __ballot(k != 0u), sat = __ballot(k != 0u && k >= a.cap), stp = __ballot((e & NHDFIT_HEADROOM_STOPPED) != 0u);
-        if (lane == 0u) {
-            s_tot[1] += (unsigned long long)popc64(room); s_tot[3] += (unsigned long long)popc64(sat);
-            s_tot[4] += (unsigned long long)popc64(stp); s_tot[5] += (unsigned long long)popc64(listed_word);
-        }
+        HeadroomTally{s_tot}.chunk(e, a.cap, listed_word, lane);
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
         __builtin_amdgcn_wave_barrier();                                 // (the entries are read; the next chunk clears them)
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
     __builtin_amdgcn_wave_barrier();
-    if (lane < 6u && s_tot[lane]) {                                      // one atomic per (block, template, field)
-        HeadroomSum* q = a.sum + tpl;
-        const unsigned long long v = s_tot[lane];
-        if (lane == 0u) atomicAdd(&q->replicas, v);
-        else if (lane == 1u) atomicAdd(&q->nodes_with_room, (uint32_t)v);
-        else if (lane == 2u) atomicMax(&q->max_on_one_node, (uint32_t)v);
-        else if (lane == 3u) atomicAdd(&q->saturated, (uint32_t)v);
-        else if (lane == 4u) atomicAdd(&q->stopped, (uint32_t)v);
-        else atomicSub(&q->not_evaluated, (uint32_t)v);                  // k_headroom counted them; they have a figure now
-    }
+    HeadroomTally{s_tot}.flush<true>(a.sum + tpl, lane);                 // (slot 5: the nodes evaluated here leave not_evaluated)
 }

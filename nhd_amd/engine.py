@@ -2,6 +2,7 @@
 from __future__ import annotations
 
 import ctypes
+import operator
 from typing import Optional, Tuple
 
 import numpy as np
@@ -290,69 +291,53 @@ class Engine:
             self._chk(self.lib.nhdfit_big_find(self.ctx, _p(reqs), P, float(now), _p(cand), _p(score), _p(maps)))
         return score, maps
 
-    # ---- explain: the stage at which each node turned each pod away (nhdfit_explain / nhdfit_explain_big) ----------------
-    def explain(self, reqs: np.ndarray, now: float, cand: Optional[np.ndarray] = None, per_node: bool = False):
-        """(counts [P][STAGES] uint32, stages [P][n] uint8 or None) for ordinary (pack.REQ) or big (pack.BIG_REQ) requests.
-        Nodes outside `cand` count as NOT_CANDIDATE; nothing of the mirror changes."""
-        reqs = np.ascontiguousarray(reqs)
+    # ---- the query entries: explain, headroom, headroom_general, headroom_limits -----------------------------------------------------
+    def _query(self, fn, reqs: np.ndarray, cand: Optional[np.ndarray], outputs, before=(), after=(), last=()):
+        """One query entry: allocates its outputs - `outputs`: per output (shape behind [P], dtype), or None for one the caller did not
+        ask for - normalises and checks `cand`, and calls fn(ctx, reqs, P, *before, cand, *after, *outputs, *last).  Nodes outside
+        `cand` are no candidates; nothing of the mirror changes."""
         P = len(reqs)
-        counts = np.zeros((P, STAGES), np.uint32)
-        stages = np.zeros((P, self.n), np.uint8) if per_node else None
+        outs = tuple(None if o is None else np.zeros((P,) + o[0], o[1]) for o in outputs)
         if cand is not None:
             cand = np.ascontiguousarray(cand, dtype=np.uint64)
             assert cand.shape == ((self.n + 63) // 64,)
         if P:
-            fn = self.lib.nhdfit_explain_big if reqs.dtype == pack.BIG_REQ else self.lib.nhdfit_explain
-            self._chk(fn(self.ctx, _p(reqs), P, float(now), _p(cand), _p(counts), _p(stages)))
-        return counts, stages
+            self._chk(fn(self.ctx, _p(reqs), P, *before, _p(cand), *after, *[_p(o) for o in outs], *last))
+        return outs
 
-    # ---- headroom: how many more replicas of each template every node can take (nhdfit_headroom) ------------------------------
-    def headroom(self, reqs: np.ndarray, cand: Optional[np.ndarray] = None, max_per_node: int = 512, per_node: bool = False,
-                 _general: bool = False):
+    def explain(self, reqs: np.ndarray, now: float, cand: Optional[np.ndarray] = None, per_node: bool = False):
+        """(counts [P][STAGES] uint32, stages [P][n] uint8 or None) for ordinary (pack.REQ) or big (pack.BIG_REQ) requests: the stage
+        at which each node turned each pod away (nhdfit_explain / nhdfit_explain_big).  Nodes outside `cand` count as NOT_CANDIDATE."""
+        reqs = np.ascontiguousarray(reqs)
+        fn = self.lib.nhdfit_explain_big if reqs.dtype == pack.BIG_REQ else self.lib.nhdfit_explain
+        return self._query(fn, reqs, cand, [((STAGES,), np.uint32), ((self.n,), np.uint8) if per_node else None], before=(float(now),))
+
+    def _headroom(self, fn, reqs, cand, max_per_node, per_node, limits=False, last=()):
+        outputs = [((), pack.HEADROOM_SUM), ((self.n,), np.uint16) if per_node else None]
+        if limits:
+            outputs += [((STAGES,), np.uint32), ((self.n,), np.uint8) if per_node else None]
+        return self._query(fn, np.ascontiguousarray(reqs, dtype=pack.REQ), cand, outputs, after=(int(max_per_node),), last=last)
+
+    def headroom(self, reqs: np.ndarray, cand: Optional[np.ndarray] = None, max_per_node: int = 512, per_node: bool = False):
         """(sums [P] pack.HEADROOM_SUM, entries [P][n] uint16 or None) for ordinary requests (pack.REQ): per node the replicas that
-        fit back to back (pack.HEADROOM_COUNT_MASK) and the STOPPED / NOT_EVALUATED bits.  Nodes outside `cand` have 0; nothing of
-        the mirror changes."""
-        reqs = np.ascontiguousarray(reqs, dtype=pack.REQ)
-        P = len(reqs)
-        sums = np.zeros(P, pack.HEADROOM_SUM)
-        counts = np.zeros((P, self.n), np.uint16) if per_node else None
-        if cand is not None:
-            cand = np.ascontiguousarray(cand, dtype=np.uint64)
-            assert cand.shape == ((self.n + 63) // 64,)
-        if P:
-            fn = self.lib.nhdfit_headroom_general if _general else self.lib.nhdfit_headroom
-            self._chk(fn(self.ctx, _p(reqs), P, _p(cand), int(max_per_node), _p(sums), _p(counts)))
-        return sums, counts
+        fit back to back (pack.HEADROOM_COUNT_MASK) and the STOPPED / NOT_EVALUATED bits (nhdfit_headroom).  Nodes outside `cand`
+        have 0."""
+        return self._headroom(self.lib.nhdfit_headroom, reqs, cand, max_per_node, per_node)
 
     def headroom_general(self, reqs: np.ndarray, cand: Optional[np.ndarray] = None, max_per_node: int = 512, per_node: bool = False):
         """headroom() with a figure for every candidate held as a wide record - wide nodes, every node of an ENABLE_SHARING mirror -
         instead of NOT_EVALUATED (nhdfit_headroom_general); the nodes of the planes are answered as headroom() answers them."""
-        return self.headroom(reqs, cand=cand, max_per_node=max_per_node, per_node=per_node, _general=True)
+        return self._headroom(self.lib.nhdfit_headroom_general, reqs, cand, max_per_node, per_node)
 
     def headroom_limits(self, reqs: np.ndarray, cand: Optional[np.ndarray] = None, max_per_node: int = 512, per_node: bool = False,
                         _slab_bytes: Optional[int] = None):
         """(sums, entries or None, limits [P][STAGES] uint32, stages [P][n] uint8 or None): headroom() - the same sums and entries -
         and the stage that ended each node's run (nhdfit_headroom_limits): per template the nodes per stage, and per node the stage
         code or pack.LIMIT_NONE where the entry is flagged.  `_slab_bytes`: the device-memory budget of the runs' final states (tests:
-        a small one makes the call take several slabs of templates)."""
-        reqs = np.ascontiguousarray(reqs, dtype=pack.REQ)
-        P = len(reqs)
-        sums = np.zeros(P, pack.HEADROOM_SUM)
-        counts = np.zeros((P, self.n), np.uint16) if per_node else None
-        limits = np.zeros((P, STAGES), np.uint32)
-        stages = np.zeros((P, self.n), np.uint8) if per_node else None
-        if cand is not None:
-            cand = np.ascontiguousarray(cand, dtype=np.uint64)
-            assert cand.shape == ((self.n + 63) // 64,)
-        if P:
-            args = (self.ctx, _p(reqs), P, _p(cand), int(max_per_node), _p(sums), _p(counts), _p(limits), _p(stages))
-            if _slab_bytes is None:
-                self._chk(self.lib.nhdfit_headroom_limits(*args))
-            else:                                                   # the library's entry outside include/nhdfit.h that takes the budget
-                fn = self.lib.nhdfit_headroom_limits_slab
-                fn.restype, fn.argtypes = ctypes.c_int, _lib._SIGS["nhdfit_headroom_limits"][1] + [ctypes.c_uint64]
-                self._chk(fn(*args, int(_slab_bytes)))
-        return sums, counts, limits, stages
+        a small one makes the call take several slabs of templates; the library's entry outside include/nhdfit.h takes it)."""
+        if _slab_bytes is None:
+            return self._headroom(self.lib.nhdfit_headroom_limits, reqs, cand, max_per_node, per_node, limits=True)
+        return self._headroom(self.lib.nhdfit_headroom_limits_slab, reqs, cand, max_per_node, per_node, limits=True, last=(int(_slab_bytes),))
 
     def big_commit(self, node: int, req: np.ndarray, mapping: np.ndarray, busy_time: float) -> np.ndarray:
         """The commit step of a big request on node `node` (ordinary or wide): updates the mirror, returns pack.BIG_PLACEMENT."""
@@ -721,127 +706,76 @@ class GroupEngine:
                 maps[own] = mp[own]
         return score, (maps if want_map else None)
 
+    # ---- the query entries over every shard ------------------------------------------------------------------------------------------
+    def _query(self, reqs: np.ndarray, cand: Optional[np.ndarray], per_node: bool, outputs, group_entry: Optional[str], shard_call,
+               before=(), after=()):
+        """One query over every shard.  `outputs` states the entry's results in their order: (shape behind [P], dtype, merge) for one
+        the shards' parts are merged into - merge(total, part) - and (None, dtype) for a per-node one, [P][n] in global node order
+        (None without `per_node`).  With a group - and a `group_entry` for these requests - libnhdfit's group entry is called:
+        entry(group, reqs, P, *before, masks, *after, *outputs), one pointer per shard for the masks and the per-node outputs;
+        otherwise shard_call(shard, mask) answers for every shard that has nodes."""
+        P = len(reqs)
+        out = [np.zeros((P,) + o[0], o[1]) if o[0] is not None else np.zeros((P, self.n), o[1]) if per_node else None for o in outputs]
+        if cand is not None:
+            cand = np.ascontiguousarray(cand, dtype=np.uint64)
+        masks = [None if cand is None else np.ascontiguousarray(cand[lo // 64:(hi + 63) // 64]) for lo, hi in self._bounds]
+        if not P:
+            return tuple(out)
+        scattered = [j for j, o in enumerate(outputs) if o[0] is None and per_node]
+        parts = {j: [None] * len(self.shards) for j in scattered}
+        if self.group is not None and group_entry is not None:
+            def pointers(arrays):
+                return (ctypes.c_void_p * len(arrays))(*[None if x is None else x.ctypes.data for x in arrays])
+            for j in scattered:
+                parts[j] = [np.zeros((P, hi - lo), outputs[j][1]) if hi > lo else None for lo, hi in self._bounds]
+            args = [_p(out[j]) if o[0] is not None else pointers(parts[j]) if per_node else None for j, o in enumerate(outputs)]
+            rc = getattr(self.lib, group_entry)(self.group, _p(reqs), P, *before, pointers(masks) if cand is not None else None, *after, *args)
+            if rc != 0:
+                raise _lib.NhdFitError(rc, (self.lib.nhdfit_group_last_error(self.group) or b"?").decode())
+        else:
+            for k, s in enumerate(self.shards):
+                if self._bounds[k][1] > self._bounds[k][0]:
+                    for j, (o, part) in enumerate(zip(outputs, shard_call(s, masks[k]))):
+                        if o[0] is not None:
+                            o[2](out[j], part)
+                        elif per_node:
+                            parts[j][k] = part
+        for j in scattered:
+            for (lo, hi), part in zip(self._bounds, parts[j]):
+                if part is not None:
+                    out[j][:, lo:hi] = part
+        return tuple(out)
+
     def explain(self, reqs: np.ndarray, now: float, cand: Optional[np.ndarray] = None, per_node: bool = False):
         """Engine.explain over every shard: counts summed over the devices (nhdfit_group_explain for ordinary requests; big ones
         shard by shard), stages put together in global node order."""
         reqs = np.ascontiguousarray(reqs)
-        P = len(reqs)
-        counts = np.zeros((P, STAGES), np.uint32)
-        stages = np.zeros((P, self.n), np.uint8) if per_node else None
-        if cand is not None:
-            cand = np.ascontiguousarray(cand, dtype=np.uint64)
-        masks = [None if cand is None else np.ascontiguousarray(cand[lo // 64:(hi + 63) // 64]) for lo, hi in self._bounds]
-        if not P:
-            return counts, stages
-        if self.group is not None and reqs.dtype != pack.BIG_REQ:
-            parts = [np.zeros((P, hi - lo), np.uint8) if per_node and hi > lo else None for lo, hi in self._bounds]
-            cptr = (ctypes.c_void_p * len(self.shards))(*[None if m is None else m.ctypes.data for m in masks])
-            sptr = (ctypes.c_void_p * len(self.shards))(*[None if x is None else x.ctypes.data for x in parts])
-            rc = self.lib.nhdfit_group_explain(self.group, _p(reqs), P, float(now), cptr if cand is not None else None, _p(counts),
-                                               sptr if per_node else None)
-            if rc != 0:
-                raise _lib.NhdFitError(rc, (self.lib.nhdfit_group_last_error(self.group) or b"?").decode())
-        else:
-            parts = []
-            for k, s in enumerate(self.shards):
-                lo, hi = self._bounds[k]
-                if hi > lo:
-                    c, st = s.explain(reqs, now, cand=masks[k], per_node=per_node)
-                    counts += c
-                    parts.append(st)
-                else:
-                    parts.append(None)
-        if per_node:
-            for (lo, hi), st in zip(self._bounds, parts):
-                if st is not None:
-                    stages[:, lo:hi] = st
-        return counts, stages
+        return self._query(reqs, cand, per_node, [((STAGES,), np.uint32, operator.iadd), (None, np.uint8)],
+                           None if reqs.dtype == pack.BIG_REQ else "nhdfit_group_explain",
+                           lambda s, mask: s.explain(reqs, now, cand=mask, per_node=per_node), before=(float(now),))
+
+    def _headroom(self, method: str, reqs, cand, max_per_node, per_node, limits=False):
+        reqs = np.ascontiguousarray(reqs, dtype=pack.REQ)
+        outputs = [((), pack.HEADROOM_SUM, _add_headroom_sums), (None, np.uint16)]
+        if limits:
+            outputs += [((STAGES,), np.uint32, operator.iadd), (None, np.uint8)]
+        return self._query(reqs, cand, per_node, outputs, "nhdfit_group_" + method,
+                           lambda s, mask: getattr(s, method)(reqs, cand=mask, max_per_node=max_per_node, per_node=per_node),
+                           after=(int(max_per_node),))
+
+    def headroom(self, reqs: np.ndarray, cand: Optional[np.ndarray] = None, max_per_node: int = 512, per_node: bool = False):
+        """Engine.headroom over every shard: the sums merged over the devices (nhdfit_group_headroom), the entries put together in
+        global node order."""
+        return self._headroom("headroom", reqs, cand, max_per_node, per_node)
 
     def headroom_general(self, reqs: np.ndarray, cand: Optional[np.ndarray] = None, max_per_node: int = 512, per_node: bool = False):
         """Engine.headroom_general over every shard (nhdfit_group_headroom_general), as headroom()."""
-        return self.headroom(reqs, cand=cand, max_per_node=max_per_node, per_node=per_node, _general=True)
-
-    def headroom(self, reqs: np.ndarray, cand: Optional[np.ndarray] = None, max_per_node: int = 512, per_node: bool = False,
-                 _general: bool = False):
-        """Engine.headroom over every shard: the sums added over the devices (nhdfit_group_headroom), the entries put together in
-        global node order."""
-        reqs = np.ascontiguousarray(reqs, dtype=pack.REQ)
-        P = len(reqs)
-        sums = np.zeros(P, pack.HEADROOM_SUM)
-        counts = np.zeros((P, self.n), np.uint16) if per_node else None
-        if cand is not None:
-            cand = np.ascontiguousarray(cand, dtype=np.uint64)
-        masks = [None if cand is None else np.ascontiguousarray(cand[lo // 64:(hi + 63) // 64]) for lo, hi in self._bounds]
-        if not P:
-            return sums, counts
-        if self.group is not None:
-            parts = [np.zeros((P, hi - lo), np.uint16) if per_node and hi > lo else None for lo, hi in self._bounds]
-            cptr = (ctypes.c_void_p * len(self.shards))(*[None if m is None else m.ctypes.data for m in masks])
-            sptr = (ctypes.c_void_p * len(self.shards))(*[None if x is None else x.ctypes.data for x in parts])
-            fn = self.lib.nhdfit_group_headroom_general if _general else self.lib.nhdfit_group_headroom
-            rc = fn(self.group, _p(reqs), P, cptr if cand is not None else None, int(max_per_node), _p(sums), sptr if per_node else None)
-            if rc != 0:
-                raise _lib.NhdFitError(rc, (self.lib.nhdfit_group_last_error(self.group) or b"?").decode())
-        else:
-            parts = []
-            for k, s in enumerate(self.shards):
-                lo, hi = self._bounds[k]
-                if hi > lo:
-                    call = s.headroom_general if _general else s.headroom
-                    sm, ct = call(reqs, cand=masks[k], max_per_node=max_per_node, per_node=per_node)
-                    _add_headroom_sums(sums, sm)
-                    parts.append(ct)
-                else:
-                    parts.append(None)
-        if per_node:
-            for (lo, hi), ct in zip(self._bounds, parts):
-                if ct is not None:
-                    counts[:, lo:hi] = ct
-        return sums, counts
+        return self._headroom("headroom_general", reqs, cand, max_per_node, per_node)
 
     def headroom_limits(self, reqs: np.ndarray, cand: Optional[np.ndarray] = None, max_per_node: int = 512, per_node: bool = False):
-        """Engine.headroom_limits over every shard: sums and histograms added over the devices (nhdfit_group_headroom_limits), entries
-        and stages put together in global node order."""
-        reqs = np.ascontiguousarray(reqs, dtype=pack.REQ)
-        P = len(reqs)
-        sums = np.zeros(P, pack.HEADROOM_SUM)
-        counts = np.zeros((P, self.n), np.uint16) if per_node else None
-        limits = np.zeros((P, STAGES), np.uint32)
-        stages = np.zeros((P, self.n), np.uint8) if per_node else None
-        if cand is not None:
-            cand = np.ascontiguousarray(cand, dtype=np.uint64)
-        masks = [None if cand is None else np.ascontiguousarray(cand[lo // 64:(hi + 63) // 64]) for lo, hi in self._bounds]
-        if not P:
-            return sums, counts, limits, stages
-        if self.group is not None:
-            parts = [np.zeros((P, hi - lo), np.uint16) if per_node and hi > lo else None for lo, hi in self._bounds]
-            sparts = [np.zeros((P, hi - lo), np.uint8) if per_node and hi > lo else None for lo, hi in self._bounds]
-            cptr = (ctypes.c_void_p * len(self.shards))(*[None if m is None else m.ctypes.data for m in masks])
-            kptr = (ctypes.c_void_p * len(self.shards))(*[None if x is None else x.ctypes.data for x in parts])
-            sptr = (ctypes.c_void_p * len(self.shards))(*[None if x is None else x.ctypes.data for x in sparts])
-            rc = self.lib.nhdfit_group_headroom_limits(self.group, _p(reqs), P, cptr if cand is not None else None, int(max_per_node), _p(sums),
-                                                       kptr if per_node else None, _p(limits), sptr if per_node else None)
-            if rc != 0:
-                raise _lib.NhdFitError(rc, (self.lib.nhdfit_group_last_error(self.group) or b"?").decode())
-        else:
-            parts, sparts = [], []
-            for k, s in enumerate(self.shards):
-                lo, hi = self._bounds[k]
-                if hi > lo:
-                    sm, ct, lm, st = s.headroom_limits(reqs, cand=masks[k], max_per_node=max_per_node, per_node=per_node)
-                    _add_headroom_sums(sums, sm)
-                    limits += lm
-                    parts.append(ct)
-                    sparts.append(st)
-                else:
-                    parts.append(None)
-                    sparts.append(None)
-        if per_node:
-            for (lo, hi), ct, st in zip(self._bounds, parts, sparts):
-                if ct is not None:
-                    counts[:, lo:hi] = ct
-                    stages[:, lo:hi] = st
-        return sums, counts, limits, stages
+        """Engine.headroom_limits over every shard: sums merged and histograms added over the devices (nhdfit_group_headroom_limits),
+        entries and stages put together in global node order."""
+        return self._headroom("headroom_limits", reqs, cand, max_per_node, per_node, limits=True)
 
     def big_commit(self, node: int, req, mapping, busy_time):
         k = self._shard_of(node)

@@ -758,6 +758,26 @@ class HipMatcher:
         """ExplainNodes for one pod."""
         return self.ExplainNodes(nl, [top], now=now, per_node=per_node)[0]
 
+    def _without_unmirrored(self, cand: Optional[np.ndarray]) -> Tuple[Optional[np.ndarray], List[int]]:
+        """(`cand` without the nodes the device does not hold, their indices): a stage query leaves them out of the call - their
+        placeholders would be charged to a stage - and reports them on their own."""
+        off = [self._index[nm] for nm in self.packer.unmirrored if nm in self._index]
+        if off:
+            n = len(self._names)
+            bits = np.zeros(((n + 63) // 64) * 64, dtype=bool)
+            if cand is None:
+                bits[:n] = True
+            else:
+                bits[:] = np.unpackbits(cand.view(np.uint8), bitorder="little").astype(bool)
+            bits[off] = False
+            cand = np.ascontiguousarray(np.packbits(bits.reshape(-1, 64), axis=1, bitorder="little").view("<u8").reshape(-1))
+        return cand, off
+
+    def _outside(self, cand: Optional[np.ndarray]) -> int:
+        """Nodes of the mirror outside `cand` - not in the caller's `nl`, or unmirrored: the device charges them NOT_CANDIDATE."""
+        n = len(self._names)
+        return 0 if cand is None else n - int(np.unpackbits(cand.view(np.uint8), bitorder="little")[:n].sum())
+
     def ExplainNodes(self, nl: Dict[str, object], tops: Sequence[object], pod_groups: Optional[Sequence[Sequence[str]]] = None,
                      now: Optional[float] = None, per_node: bool = False) -> List[Explanation]:
         """Why each node of `nl` turned each pod of `tops` away, counted on the device (nhdfit_explain): one Explanation per pod,
@@ -777,17 +797,8 @@ class HipMatcher:
         now = self.clock() if now is None else now
         cand = self._sync_mirror(nl)
         n = len(self._names)
-        # nodes the device does not hold are left out of the call (they would read as placeholders) and reported on their own
-        off = [self._index[nm] for nm in self.packer.unmirrored if nm in self._index]
-        if off:
-            bits = np.zeros(((n + 63) // 64) * 64, dtype=bool)
-            if cand is None:
-                bits[:n] = True
-            else:
-                bits[:] = np.unpackbits(cand.view(np.uint8), bitorder="little").astype(bool)
-            bits[off] = False
-            cand = np.ascontiguousarray(np.packbits(bits.reshape(-1, 64), axis=1, bitorder="little").view("<u8").reshape(-1))
-        outside = n - (n if cand is None else int(np.unpackbits(cand.view(np.uint8)).sum()))
+        cand, off = self._without_unmirrored(cand)
+        outside = self._outside(cand)
         n_unmirrored = sum(1 for nm in nl if nm in self.packer.unmirrored)
         is_big = [pack.needs_general_path(top) for top in tops]
         big_recs = {}
@@ -904,18 +915,7 @@ class HipMatcher:
                 self.packer.close_signatures()             # every NIC state a commit can produce has a signature
                 self.engine.set_dictionary(self.packer)
                 if limits:
-                    # nodes the device does not hold are left out of the call, as ExplainNodes leaves them out (their placeholders would
-                    # be charged to a stage; their count is 0 either way) and reported on their own
-                    off = [self._index[nm] for nm in self.packer.unmirrored if nm in self._index]
-                    if off:
-                        n = len(self._names)
-                        bits = np.zeros(((n + 63) // 64) * 64, dtype=bool)
-                        if cand is None:
-                            bits[:n] = True
-                        else:
-                            bits[:] = np.unpackbits(cand.view(np.uint8), bitorder="little").astype(bool)
-                        bits[off] = False
-                        cand = np.ascontiguousarray(np.packbits(bits.reshape(-1, 64), axis=1, bitorder="little").view("<u8").reshape(-1))
+                    cand, off = self._without_unmirrored(cand)     # (as ExplainNodes: their count is 0 either way)
                     sums, counts, hist, stages = self.engine.headroom_limits(reqs, cand=cand, max_per_node=int(max_per_node), per_node=per_node)
                 elif general:
                     sums, counts = self.engine.headroom_general(reqs, cand=cand, max_per_node=int(max_per_node), per_node=per_node)
@@ -931,10 +931,7 @@ class HipMatcher:
         order = np.fromiter((self._index[nm] for nm in nl), dtype=np.int64, count=len(nl)) if per_node else None
         outside = 0
         if limits and hist is not None:
-            # the device charges NOT_CANDIDATE to every node of the mirror outside `cand`: nodes that are not in `nl`, and the unmirrored ones
-            n = len(self._names)
-            outside = 0 if cand is None else n - int(np.unpackbits(cand.view(np.uint8), bitorder="little")[:n].sum())
-            off = [self._index[nm] for nm in self.packer.unmirrored if nm in self._index]
+            outside = self._outside(cand)
             if per_node and off:
                 stages[:, off] = UNMIRRORED
         out = []

@@ -165,6 +165,17 @@ _WAVE_BIG_FROM, _WAVE_BIG_TO = "// ---- the winner's mapping with the wavefront'
 _wave = None
 
 
+def cut_section(header, start, end, must_contain, out):
+    """Writes the lines of a kernel header from the one that begins with `start` up to the one that begins with `end`, unmodified,
+    into `out`: device source text an emulator includes.  `must_contain`: the function the section is cut out for."""
+    lines = open(header).read().split("\n")
+    a = next(i for i, ln in enumerate(lines) if ln.startswith(start))
+    b = next(i for i, ln in enumerate(lines) if ln.startswith(end))
+    assert a < b and any(must_contain in ln for ln in lines[a:b])
+    with open(out, "w") as f:
+        f.write("\n".join(lines[a:b]) + "\n")
+
+
 def wave_lib():
     """Builds tests/harness/wave_emul.cpp around the commit section of nhd_amd/csrc/seq2_kernel.h (cut out unmodified)."""
     global _wave
@@ -176,24 +187,9 @@ def wave_lib():
     deps = [WAVE_SRC, kernel, kernel1, kernel2] + [os.path.join(HERE, "..", "..", "nhd_amd", "csrc", f) for f in ("fit_core.h", "seq_core.h", "commit_core.h", "winner_map.h", "set_states.h", "wide_core.h")] + \
            [os.path.join(HERE, "..", "..", "include", "nhdfit.h")]
     if not os.path.exists(WAVE_SO) or any(os.path.getmtime(d) > os.path.getmtime(WAVE_SO) for d in deps):
-        lines = open(kernel).read().split("\n")
-        a = next(i for i, ln in enumerate(lines) if ln.startswith(_WAVE_FROM))
-        b = next(i for i, ln in enumerate(lines) if ln.startswith(_WAVE_TO))
-        assert a < b and any("commit_node_wave" in ln for ln in lines[a:b])
-        with open(WAVE_INC, "w") as f:
-            f.write("\n".join(lines[a:b]) + "\n")
-        lines = open(kernel1).read().split("\n")
-        a = next(i for i, ln in enumerate(lines) if ln.startswith(_WAVE_MAP_FROM))
-        b = next(i for i, ln in enumerate(lines) if ln.startswith(_WAVE_MAP_TO))
-        assert a < b and any("map_on_state_wave" in ln for ln in lines[a:b])
-        with open(WAVE_MAP_INC, "w") as f:
-            f.write("\n".join(lines[a:b]) + "\n")
-        lines = open(kernel2).read().split("\n")
-        a = next(i for i, ln in enumerate(lines) if ln.startswith(_WAVE_BIG_FROM))
-        b = next(i for i, ln in enumerate(lines) if ln.startswith(_WAVE_BIG_TO))
-        assert a < b and any("wide_map_wave" in ln for ln in lines[a:b])
-        with open(WAVE_BIG_INC, "w") as f:
-            f.write("\n".join(lines[a:b]) + "\n")
+        cut_section(kernel, _WAVE_FROM, _WAVE_TO, "commit_node_wave", WAVE_INC)
+        cut_section(kernel1, _WAVE_MAP_FROM, _WAVE_MAP_TO, "map_on_state_wave", WAVE_MAP_INC)
+        cut_section(kernel2, _WAVE_BIG_FROM, _WAVE_BIG_TO, "wide_map_wave", WAVE_BIG_INC)
         tmp = f"{WAVE_SO}.{os.getpid()}.tmp"
         subprocess.check_call(["g++", "-O2", "-std=c++20", "-ffp-contract=off", "-shared", "-fPIC", "-pthread", WAVE_SRC, "-o", tmp])
         os.replace(tmp, WAVE_SO)

@@ -41,8 +41,6 @@ extern "C" int hx_headroom_general(const nhdfit_plane0* p0, const nhdfit_plane1*
                                    hrh::Sum* sums, uint16_t* counts) {
     const hrh::Dictionary d = hrh::make_dictionary(fcmax, fgmax, gs, ngs, caps, ncls, sig_off, nsig, pool_off, pool_glimit, cc);
     if (!d.ok) return -1;
-    const SigTable sigs = d.sigs();
-    const MapTables mt{nullptr, nullptr, SetStates{nullptr, nullptr, nullptr, 0}};
     std::vector<int16_t> scratch(kWideScratchWords);
     std::vector<int32_t> slot(n, -1);
     for (uint32_t w = 0; w < n_wide; ++w)
@@ -50,8 +48,6 @@ extern "C" int hx_headroom_general(const nhdfit_plane0* p0, const nhdfit_plane1*
     for (uint32_t p = 0; p < P; ++p) {
         const nhdfit_req& r = reqs[p];
         const hrh::Masks m = hrh::make_masks(r, d);
-        const LoneMasks t = m.view();
-        const bool pci = r.map_type == NHDFIT_MAP_PCI;
         hrh::Sum s;
         std::memset(&s, 0, sizeof s);
         s.form = hrh::form_of(r) | (n_wide ? NHDFIT_HEADROOM_FORM_WIDE : 0u);
@@ -65,21 +61,7 @@ extern "C" int hx_headroom_general(const nhdfit_plane0* p0, const nhdfit_plane1*
             } else if (listed) {                                        // (headroom_twin.cpp's loop)
                 NodeState st{p0[v], p1[v], p2[v], p3[v], p4[v]};
                 nhdfit_detail dd = det[v];
-                uint32_t k = 0;
-                for (;;) {
-                    const NodeIdx ni = node_index(st.p0, st.p1, st.p2, st.p4, d.fc_dim, d.fg_dim, d.ngs);
-                    if (!lone_pod_fits(t, m.h, ni, st.p3, false, gs)) break;
-                    if (k >= cap) break;
-                    nhdfit_mapping mp;
-                    std::memset(&mp, 0, sizeof mp);
-                    if (!map_on_state(r, st, dd, caps, lone_nic_bits(t, pci, st.p3), mt, mp)) break;
-                    bool nic_missing = false;
-                    for (uint32_t g = 0; g < r.n_groups; ++g) nic_missing |= (uint32_t)mp.nic_idx[g] >= dd.nic_cnt[mp.nic_numa[g] & 1];
-                    nhdfit_placement pl;
-                    if (nic_missing || commit_node(st, dd, r, mp, 0.0, sigs, pl) != kCommitOk) { e = NHDFIT_HEADROOM_STOPPED; break; }
-                    ++k;
-                }
-                e |= k;
+                e = hrh::plane_run(st, dd, r, m, d, cap);
             }
             hrh::account(s, e, cap);
             if (counts) counts[(size_t)p * n + v] = (uint16_t)e;

@@ -44,12 +44,7 @@ def wave_lib():
         harness.wave_lib()                                  # (wave_emul.cpp's own .inc files)
         kernel = os.path.join(ht.CSRC, "wide_room_kernel.h")
         if ht._stale(WAVE_SO, [WAVE_SRC, harness.WAVE_SRC, harness.WAVE_SO, kernel] + ht._headers()):
-            lines = open(kernel).read().split("\n")
-            a = next(i for i, ln in enumerate(lines) if ln.startswith(_FROM))
-            b = next(i for i, ln in enumerate(lines) if ln.startswith(_TO))
-            assert a < b and any("wide_room_run_wave" in ln for ln in lines[a:b])
-            with open(WAVE_INC, "w") as f:
-                f.write("\n".join(lines[a:b]) + "\n")
+            harness.cut_section(kernel, _FROM, _TO, "wide_room_run_wave", WAVE_INC)
             tmp = f"{WAVE_SO}.{os.getpid()}.tmp"
             subprocess.check_call(["g++", "-O2", "-std=c++20", "-ffp-contract=off", "-shared", "-fPIC", "-pthread", WAVE_SRC, "-o", tmp])
             os.replace(tmp, WAVE_SO)
@@ -61,26 +56,9 @@ def wave_lib():
 def headroom_general(packer, table, wide, share, reqs, cand=None, max_per_node=512, per_node=True):
     """(sums [P] pack.HEADROOM_SUM, entries [P][n] uint16 or None) of the scalar twin for the planes of `table` and the wide records
     `wide` (`share`: None, or their nhdfit_wide_share records in the same order)."""
-    reqs = np.ascontiguousarray(reqs, dtype=pack.REQ)
-    wide = np.ascontiguousarray(wide, dtype=pack.WIDE)
-    if share is not None:
-        share = np.ascontiguousarray(share, dtype=pack.WIDE_SHARE).reshape(-1)
-        assert len(share) == len(wide)
-    P, n = len(reqs), table.n
-    sums = np.zeros(P, pack.HEADROOM_SUM)
-    counts = np.zeros((P, n), np.uint16) if per_node else None
-    planes = [np.ascontiguousarray(getattr(table, f)) for f in ("p0", "p1", "p2", "p3", "p4", "detail")]
-    caps, sig_off, pool_off, glimit, cc, ncls, nsig, npools, ncc = packer.dictionary_arrays()
-    gs = packer.group_set_array()
-    if cand is not None:
-        cand = np.ascontiguousarray(cand, dtype=np.uint64)
-    rc = lib().hx_headroom_general(*[_p(x) for x in planes], ctypes.c_uint32(n), _p(wide) if len(wide) else None, ctypes.c_uint32(len(wide)),
-                                   _p(share) if share is not None and len(wide) else None, _p(reqs), ctypes.c_uint32(P),
-                                   ctypes.c_uint32(packer.max_cores_per_numa), ctypes.c_uint32(packer.max_gpus_per_numa), _p(gs),
-                                   ctypes.c_uint32(len(packer.group_sets)), _p(caps), ctypes.c_uint32(ncls), _p(sig_off), ctypes.c_uint32(nsig),
-                                   _p(pool_off), _p(glimit), _p(cc), _p(cand), ctypes.c_uint32(int(max_per_node)), _p(sums), _p(counts))
+    rc, out = ht.run(lib().hx_headroom_general, packer, table, wide, reqs, cand, max_per_node, per_node, share=share)
     assert rc == 0, f"{rc}: the dictionary's stream does not fit (-1) / a set of the model outgrew its table (-2)"
-    return sums, counts
+    return out
 
 
 def wide_room_wave(packer, wide, share, reqs, max_per_node=512):

@@ -104,5 +104,30 @@ inline void account(Sum& s, uint32_t e, uint32_t cap) {
     if (e & NHDFIT_HEADROOM_STOPPED) s.stopped++;
     if (e & NHDFIT_HEADROOM_NOT_EVALUATED) s.not_evaluated++;
 }
+// One node of the planes run to exhaustion over the shared headers' SCALAR forms - node_index / lone_pod_fits (fit_core.h),
+// lone_nic_bits, map_on_state (seq_core.h), commit_node (commit_core.h) - on the private copy `st` / `dd`, which is left as the run
+// ended (the mirror's state until a commit succeeds).  IsBusy() false: the busy window is not a resource.  Returns the node's entry:
+// replicas | NHDFIT_HEADROOM_STOPPED.
+inline uint32_t plane_run(NodeState& st, nhdfit_detail& dd, const nhdfit_req& r, const Masks& m, const Dictionary& d, uint32_t cap) {
+    const LoneMasks t = m.view();
+    const SigTable sigs = d.sigs();
+    const MapTables mt{nullptr, nullptr, SetStates{nullptr, nullptr, nullptr, 0}};
+    const bool pci = r.map_type == NHDFIT_MAP_PCI;
+    uint32_t k = 0;
+    for (;;) {
+        const NodeIdx ni = node_index(st.p0, st.p1, st.p2, st.p4, d.fc_dim, d.fg_dim, d.ngs);
+        if (!lone_pod_fits(t, m.h, ni, st.p3, false, d.gs)) break;
+        if (k >= cap) break;
+        nhdfit_mapping mp;
+        std::memset(&mp, 0, sizeof mp);
+        if (!map_on_state(r, st, dd, d.caps, lone_nic_bits(t, pci, st.p3), mt, mp)) break;
+        bool nic_missing = false;
+        for (uint32_t g = 0; g < r.n_groups; ++g) nic_missing |= (uint32_t)mp.nic_idx[g] >= dd.nic_cnt[mp.nic_numa[g] & 1];
+        nhdfit_placement pl;
+        if (nic_missing || commit_node(st, dd, r, mp, 0.0, sigs, pl) != kCommitOk) return k | NHDFIT_HEADROOM_STOPPED;
+        ++k;
+    }
+    return k;
+}
 inline uint32_t form_of(const nhdfit_req& r) { return req_valid(r) && r.n_groups > 3 ? NHDFIT_HEADROOM_FORM_GENERIC : NHDFIT_HEADROOM_FORM_WAVE; }
 }  // namespace hrh

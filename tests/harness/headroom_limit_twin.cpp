@@ -1,5 +1,5 @@
 // headroom_limit_twin.cpp - TEST INFRASTRUCTURE.  The host build of nhdfit_headroom_limits: headroom_twin.cpp's scalar run of every
-// node (node_index / lone_pod_fits, lone_nic_bits, map_on_state, commit_node on a private copy), and then - what k_limit_stage
+// node (hrh::plane_run on a private copy), and then - what k_limit_stage
 // (nhd_amd/csrc/limit_kernel.h) does on the device - wide_view of the copy as the run left it and explain_stage (explain_core.h)
 // with nothing busy.  It is NOT part of libnhdfit.so and nothing in nhd_amd/ loads it.
 #include "headroom_host.h"
@@ -15,13 +15,9 @@ extern "C" int hx_headroom_limits(const nhdfit_plane0* p0, const nhdfit_plane1* 
                                   uint16_t* counts, uint32_t* hist, uint8_t* stage) {
     const hrh::Dictionary d = hrh::make_dictionary(fcmax, fgmax, gs, ngs, caps, ncls, sig_off, nsig, pool_off, pool_glimit, cc);
     if (!d.ok) return -1;
-    const SigTable sigs = d.sigs();
-    const MapTables mt{nullptr, nullptr, SetStates{nullptr, nullptr, nullptr, 0}};
     for (uint32_t p = 0; p < P; ++p) {
         const nhdfit_req& r = reqs[p];
         const hrh::Masks m = hrh::make_masks(r, d);
-        const LoneMasks t = m.view();
-        const bool pci = r.map_type == NHDFIT_MAP_PCI;
         hrh::Sum s;
         std::memset(&s, 0, sizeof s);
         s.form = hrh::form_of(r);
@@ -32,21 +28,7 @@ extern "C" int hx_headroom_limits(const nhdfit_plane0* p0, const nhdfit_plane1* 
             nhdfit_detail dd = det[v];
             if (listed && hrh::is_wide(wide, n_wide, v)) e = NHDFIT_HEADROOM_NOT_EVALUATED;
             else if (listed) {
-                uint32_t k = 0;
-                for (;;) {
-                    const NodeIdx ni = node_index(st.p0, st.p1, st.p2, st.p4, d.fc_dim, d.fg_dim, d.ngs);
-                    if (!lone_pod_fits(t, m.h, ni, st.p3, false, gs)) break;
-                    if (k >= cap) break;
-                    nhdfit_mapping mp;
-                    std::memset(&mp, 0, sizeof mp);
-                    if (!map_on_state(r, st, dd, caps, lone_nic_bits(t, pci, st.p3), mt, mp)) break;
-                    bool nic_missing = false;
-                    for (uint32_t g = 0; g < r.n_groups; ++g) nic_missing |= (uint32_t)mp.nic_idx[g] >= dd.nic_cnt[mp.nic_numa[g] & 1];
-                    nhdfit_placement pl;
-                    if (nic_missing || commit_node(st, dd, r, mp, 0.0, sigs, pl) != kCommitOk) { e = NHDFIT_HEADROOM_STOPPED; break; }
-                    ++k;
-                }
-                e |= k;
+                e = hrh::plane_run(st, dd, r, m, d, cap);
             }
             hrh::account(s, e, cap);
             if (counts) counts[(size_t)p * n + v] = (uint16_t)e;

@@ -4,10 +4,6 @@ import ctypes
 import os
 import subprocess
 
-import numpy as np
-
-from nhd_amd import pack
-from nhd_amd.engine import STAGES
 from tests.harness import headroom_twin as ht
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -33,25 +29,9 @@ def lib():
 def headroom_limits(packer, table, wide, reqs, cand=None, max_per_node=512, per_node=True):
     """(sums [P] pack.HEADROOM_SUM, entries [P][n] uint16 or None, limits [P][STAGES] uint32, stages [P][n] uint8 or None) of the host
     build for the planes of `table`; the nodes of the wide records `wide` are not evaluated."""
-    reqs = np.ascontiguousarray(reqs, dtype=pack.REQ)
-    wide = np.ascontiguousarray(wide, dtype=pack.WIDE)
-    P, n = len(reqs), table.n
-    sums = np.zeros(P, pack.HEADROOM_SUM)
-    counts = np.zeros((P, n), np.uint16) if per_node else None
-    hist = np.zeros((P, STAGES), np.uint32)
-    stages = np.zeros((P, n), np.uint8) if per_node else None
-    planes = [np.ascontiguousarray(getattr(table, f)) for f in ("p0", "p1", "p2", "p3", "p4", "detail")]
-    caps, sig_off, pool_off, glimit, cc, ncls, nsig, npools, ncc = packer.dictionary_arrays()
-    gs = packer.group_set_array()
-    if cand is not None:
-        cand = np.ascontiguousarray(cand, dtype=np.uint64)
-    rc = lib().hx_headroom_limits(*[_p(x) for x in planes], ctypes.c_uint32(n), _p(wide) if len(wide) else None, ctypes.c_uint32(len(wide)), _p(reqs),
-                                  ctypes.c_uint32(P), ctypes.c_uint32(packer.max_cores_per_numa), ctypes.c_uint32(packer.max_gpus_per_numa), _p(gs),
-                                  ctypes.c_uint32(len(packer.group_sets)), _p(caps), ctypes.c_uint32(ncls), _p(sig_off), ctypes.c_uint32(nsig),
-                                  _p(pool_off), _p(glimit), _p(cc), _p(cand), ctypes.c_uint32(int(max_per_node)), _p(sums), _p(counts), _p(hist),
-                                  _p(stages))
+    rc, out = ht.run(lib().hx_headroom_limits, packer, table, wide, reqs, cand, max_per_node, per_node, limits=True)
     assert rc == 0, f"{rc}: the dictionary's stream does not fit"
-    return sums, counts, hist, stages
+    return out
 
 
 class HeadroomLimitHarnessEngine(ht.HeadroomHarnessEngine):

@@ -1,9 +1,10 @@
 // headroom_twin.cpp - TEST INFRASTRUCTURE.  The host build of nhdfit_headroom: the loop k_headroom (nhd_amd/csrc/headroom_kernel.h)
-// runs per node, written over the shared headers' SCALAR forms - node_index / lone_pod_fits (fit_core.h), lone_nic_bits,
-// map_on_state (seq_core.h), commit_node (commit_core.h) - on a private copy of every node.  It is NOT part of libnhdfit.so and
+// runs per node, written over the shared headers' SCALAR forms (hrh::plane_run, headroom_host.h) on a private copy of every node,
+// and the group entries' merge of the shards' summary records (headroom_merge.h).  It is NOT part of libnhdfit.so and
 // nothing in nhd_amd/ loads it.  (The kernel's own per-node loop, with the wavefront forms, runs on emulated lanes in
 // headroom_wave_emul.cpp; tests/test_headroom_core.py holds the two to each other.)
 #include "headroom_host.h"
+#include "../../nhd_amd/csrc/headroom_merge.h"
 
 using namespace nhdfit;
 
@@ -14,13 +15,9 @@ extern "C" int hx_headroom(const nhdfit_plane0* p0, const nhdfit_plane1* p1, con
                            const uint64_t* cand, uint32_t cap, hrh::Sum* sums, uint16_t* counts) {
     const hrh::Dictionary d = hrh::make_dictionary(fcmax, fgmax, gs, ngs, caps, ncls, sig_off, nsig, pool_off, pool_glimit, cc);
     if (!d.ok) return -1;
-    const SigTable sigs = d.sigs();
-    const MapTables mt{nullptr, nullptr, SetStates{nullptr, nullptr, nullptr, 0}};
     for (uint32_t p = 0; p < P; ++p) {
         const nhdfit_req& r = reqs[p];
         const hrh::Masks m = hrh::make_masks(r, d);
-        const LoneMasks t = m.view();
-        const bool pci = r.map_type == NHDFIT_MAP_PCI;
         hrh::Sum s;
         std::memset(&s, 0, sizeof s);
         s.form = hrh::form_of(r);
@@ -31,21 +28,7 @@ extern "C" int hx_headroom(const nhdfit_plane0* p0, const nhdfit_plane1* p1, con
             else if (listed) {
                 NodeState st{p0[v], p1[v], p2[v], p3[v], p4[v]};
                 nhdfit_detail dd = det[v];
-                uint32_t k = 0;
-                for (;;) {
-                    const NodeIdx ni = node_index(st.p0, st.p1, st.p2, st.p4, d.fc_dim, d.fg_dim, d.ngs);
-                    if (!lone_pod_fits(t, m.h, ni, st.p3, false, gs)) break;            // IsBusy() false: the busy window is not a resource
-                    if (k >= cap) break;
-                    nhdfit_mapping mp;
-                    std::memset(&mp, 0, sizeof mp);
-                    if (!map_on_state(r, st, dd, caps, lone_nic_bits(t, pci, st.p3), mt, mp)) break;
-                    bool nic_missing = false;
-                    for (uint32_t g = 0; g < r.n_groups; ++g) nic_missing |= (uint32_t)mp.nic_idx[g] >= dd.nic_cnt[mp.nic_numa[g] & 1];
-                    nhdfit_placement pl;
-                    if (nic_missing || commit_node(st, dd, r, mp, 0.0, sigs, pl) != kCommitOk) { e = NHDFIT_HEADROOM_STOPPED; break; }
-                    ++k;
-                }
-                e |= k;
+                e = hrh::plane_run(st, dd, r, m, d, cap);
             }
             hrh::account(s, e, cap);
             if (counts) counts[(size_t)p * n + v] = (uint16_t)e;
@@ -53,4 +36,9 @@ extern "C" int hx_headroom(const nhdfit_plane0* p0, const nhdfit_plane1* p1, con
         sums[p] = s;
     }
     return 0;
+}
+
+// the statement libnhdfit.so's group entries run per shard (tests/test_headroom_merge.py holds engine._add_headroom_sums to it)
+extern "C" void hx_merge_headroom_sums(nhdfit_headroom_sum* sums, const nhdfit_headroom_sum* part, uint32_t P) {
+    merge_headroom_sums(sums, part, P);
 }

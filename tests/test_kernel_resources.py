@@ -46,3 +46,7 @@ def test_step_kernel_uses_no_scratch_to_speak_of(tmp_path):
     # model's scratch arrays (10 KB per lane) belong to the other instantiation only
     lean = [v for k, v in usage.items() if "k_decideILb0E" in k]
     assert len(lean) == 1 and lean[0]["ScratchSize"] <= 64, lean
+    # the wavefront form of the headroom kernel: "no private segment at all" (headroom_kernel.h) - the models that need scratch arrays
+    # belong to k_headroom<true> only
+    wave = [v for k, v in usage.items() if "k_headroomILb0E" in k]
+    assert len(wave) == 1 and wave[0]["ScratchSize"] == 0, wave
