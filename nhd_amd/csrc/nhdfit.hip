@@ -113,41 +113,25 @@ struct Rccl {
 Rccl g_rccl;
 
 // The two buffer types own their memory: a context's buffers go with the context (nhdfit_destroy names none of them).
-template <class T>
-struct DevBuf {
+template <class T, bool kPinned>
+struct Buf {
     T* p = nullptr;
     size_t cap = 0;   // elements
-    DevBuf() = default;
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-    ~DevBuf() { release(); }
+    Buf() = default;
+    Buf(const Buf&) = delete;
+    Buf& operator=(const Buf&) = delete;
+    ~Buf() { release(); }
     hipError_t reserve(size_t n) {
         if (n <= cap) return hipSuccess;
-        if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
-        hipError_t e = hipMalloc((void**)&p, n * sizeof(T));
+        release();
+        hipError_t e = kPinned ? hipHostMalloc((void**)&p, n * sizeof(T), hipHostMallocDefault) : hipMalloc((void**)&p, n * sizeof(T));
         if (e == hipSuccess) cap = n;
         return e;
     }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+    void release() { if (p) (void)(kPinned ? hipHostFree(p) : hipFree(p)); p = nullptr; cap = 0; }
 };
-
-template <class T>
-struct PinBuf {                   // page-locked host staging: async copies in both directions, no bounce buffer inside the runtime
-    T* p = nullptr;
-    size_t cap = 0;
-    PinBuf() = default;
-    PinBuf(const PinBuf&) = delete;
-    PinBuf& operator=(const PinBuf&) = delete;
-    ~PinBuf() { release(); }
-    hipError_t reserve(size_t n) {
-        if (n <= cap) return hipSuccess;
-        if (p) { (void)hipHostFree(p); p = nullptr; cap = 0; }
-        hipError_t e = hipHostMalloc((void**)&p, n * sizeof(T), hipHostMallocDefault);
-        if (e == hipSuccess) cap = n;
-        return e;
-    }
-    void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
-};
+template <class T> using DevBuf = Buf<T, false>;
+template <class T> using PinBuf = Buf<T, true>;   // page-locked host staging: async copies in both directions, no bounce buffer inside the runtime
 static_assert(!std::is_copy_constructible<DevBuf<int>>::value && !std::is_copy_assignable<DevBuf<int>>::value &&
               !std::is_copy_constructible<PinBuf<int>>::value && !std::is_copy_assignable<PinBuf<int>>::value,
               "a buffer is freed once, by its one owner");
@@ -181,6 +165,27 @@ struct QueryBufs {
     DevBuf<uint32_t> tickets; DevBuf<HeadroomSum> sum; DevBuf<uint16_t> counts;      // headroom: ticket counters, summary records, entries
     DevBuf<HeadroomFinal> final;                                 // limits: the runs' final states, a slab of templates at a time
     DevBuf<uint32_t> wide_tickets;                               // general: the wide launch's ticket counters, and behind them its flag words
+};
+
+// Buffers of mode B (nhdfit_schedule_batch; seq_kernel.h, seq2_kernel.h): sized for one batch of P pods on n nodes by one reserve.
+struct SeqBufs {
+    DevBuf<uint64_t> nogpu, taken, tile_masks; DevBuf<int32_t> touched; DevBuf<uint16_t> gl_tiles; DevBuf<UndoRec> undo; DevBuf<SeqResult> seq_out; DevBuf<nhdfit_placement> seq_place;
+    DevBuf<uint64_t> rows_t;             // pod-major verdict rows [P][chunks] of the snapshot, converted from `nm` (convert_rows_t)
+    DevBuf<uint32_t> order, seq_counters;
+    DevBuf<unsigned long long> seq_queue; DevBuf<uint32_t> seq_ctrl, seq_mat, seq_flags; DevBuf<uint4> seq_ent;   // decision-engine form of mode B (seq2_kernel.h)
+    PinBuf<uint32_t> pin_order; uint32_t tn_n = 0;   // [order | list] on their way to the device; pods without GPUs in the list
+    std::vector<SeqResult> seq_host;
+    hipError_t reserve(uint32_t P, uint32_t n, uint32_t chunks, uint32_t tiles) {
+        const size_t per_chunk = chunks ? chunks : 1, per_node = n ? n : 1;
+        hipError_t e = hipSuccess;
+        auto r = [&e](auto& buf, size_t count) { if (e == hipSuccess) e = buf.reserve(count); };
+        r(nogpu, per_chunk); r(taken, per_chunk); r(tile_masks, (size_t)tiles * 2); r(gl_tiles, tiles);
+        r(touched, per_node); r(seq_mat, per_node);
+        r(undo, P); r(seq_out, P); r(seq_place, P); r(seq_ent, P); r(order, 2 * (size_t)P); r(pin_order, 2 * (size_t)P);
+        r(rows_t, (size_t)chunks * P);           // (convert_rows_t's: SeqArgs holds its address before the first pass fills it)
+        r(seq_counters, 4); r(seq_flags, 4); r(seq_ctrl, 32);
+        return e;                                // (seq_queue is the engine's alone: reserved where the engine is admitted)
+    }
 };
 
 }  // namespace
@@ -241,7 +246,6 @@ struct nhdfit_ctx {
     PinBuf<nhdfit_req> pin_reqs; PinBuf<uint8_t> pin_wcls; PinBuf<uint64_t> pin_score; PinBuf<nhdfit_mapping> pin_maps;   // host staging of one call
     PinBuf<uint8_t> pin_items;           // the fit role's work items on their way to the device
     DevBuf<uint64_t> bitmap;             // pod-major rows [chunks][P], converted from `nm` on demand (fetch)
-    DevBuf<uint64_t> rows_t;             // ... [P][chunks] for the sequential kernels (mode B)
     DevBuf<uint64_t> cand;               // [chunks] candidate nodes of the call
     DevBuf<uint8_t> tile_wcls;           // row width class per staged tile
     DevBuf<FitItem> items; uint32_t n_items = 0;   // work items of the fit role (blocks), heaviest tiles first
@@ -264,10 +268,7 @@ struct nhdfit_ctx {
     // set-layout state machine for three-group pods (set_states.h): verified against the model on the host
     // (tests/test_pyset_emulation.py), parity-green and 10 % faster per step on the GPU than the insertion-by-insertion model (profiles/r02)
     DevBuf<uint64_t> st_info; DevBuf<uint32_t> st_next, st_asc; uint32_t st_n = 0;
-    // mode B
-    DevBuf<uint64_t> nogpu, taken, tile_masks; DevBuf<int32_t> touched; DevBuf<uint16_t> gl_tiles; std::vector<SeqResult> seq_host; DevBuf<UndoRec> undo; DevBuf<SeqResult> seq_out; DevBuf<nhdfit_placement> seq_place;
-    DevBuf<uint32_t> order, seq_counters;
-    DevBuf<unsigned long long> seq_queue; DevBuf<uint32_t> seq_ctrl, seq_mat, seq_flags; DevBuf<uint4> seq_ent;   // decision-engine form of mode B (seq2_kernel.h)
+    SeqBufs seq;                         // mode B
     bool seq_general = tune_env("NHDFIT_SEQ_GENERAL") != nullptr;   // tuning aid: the one-block kernel for every batch
     DevBuf<uint64_t> sig_keys; DevBuf<uint32_t> sig_ids; uint32_t sig_mask = 0;   // canonical NIC-state key -> signature id (commit_core.h)
     bool use_cand = false, want_bitmap = true, want_map = true;
@@ -285,7 +286,6 @@ struct nhdfit_ctx {
     uint8_t* findn_host = nullptr; size_t findn_cap = 0;
     DevBuf<uint32_t> findn_sync; uint32_t findn_sync_words = 0;
     bool batch_find = tune_env("NHDFIT_NO_BATCH_FIND") == nullptr;   // tuning aid: batches of more than one tile through the staged path
-    PinBuf<uint32_t> pin_order; uint32_t tn_n = 0;   // mode B: [order | list] on their way to the device; pods without GPUs in the list
     bool reqs_deferred = false, wcls_deferred = false;   // the staged batch's request records / tile classes are in the page-locked block only (finish_deferred_copies)
     bool lone_pod = tune_env("NHDFIT_NO_LONE_POD") == nullptr;      // one pod: the table-free launch (k_find1); tuning aid: NHDFIT_NO_LONE_POD=1 takes k_find
 
@@ -341,6 +341,28 @@ int fail(nhdfit_ctx* c, int code, const char* fmt, ...) {
         if (rc_) return rc_;                             \
     } while (0)
 
+// A setting of the context for the length of a scope: it goes back to what it was on every way out, so the code in between can TRY.
+template <class T>
+struct Scoped {
+    T& ref; T saved;
+    Scoped(T& r, T now) : ref(r), saved(r) { ref = now; }
+    ~Scoped() { ref = saved; }
+};
+
+// A caller's mapping in front of a commit step: its entries index per-socket arrays / 16-entry NIC tables on the device.
+template <class Map>
+int check_mapping(nhdfit_ctx* c, const Map* map, uint32_t n_groups, int numa_lim) {
+    for (uint32_t g = 0; g <= n_groups; ++g) {
+        if (map->cpu[g] < 0 || map->cpu[g] >= numa_lim) return fail(c, NHDFIT_E_INVAL, "mapping: cpu[%u] = %d is not a NUMA node", g, (int)map->cpu[g]);
+        if (g == n_groups) break;
+        if (map->gpu[g] < 0 || map->gpu[g] >= numa_lim || map->nic_numa[g] < 0 || map->nic_numa[g] >= numa_lim)
+            return fail(c, NHDFIT_E_INVAL, "mapping: group %u sits on NUMA node %d / its NIC on %d", g, (int)map->gpu[g], (int)map->nic_numa[g]);
+        if (map->nic_idx[g] < 0 || map->nic_idx[g] >= NHDFIT_MAX_NICS_PER_NUMA)
+            return fail(c, NHDFIT_E_INVAL, "mapping: group %u uses NIC ordinal %d", g, (int)map->nic_idx[g]);
+    }
+    return NHDFIT_OK;
+}
+
 // Whatever puts work on a stream - launch, async copy or fill, event record, wait for an event, collective - takes the handle from
 // c->streams.use(k), which marks stream k; c->streams.wait(k) clears the mark (host_streams.h).  The shortcuts that skip a wait
 // (sync_all, stage_requests, nhdfit_commit) read those marks and nothing else.
@@ -385,8 +407,68 @@ int drain_events(nhdfit_ctx* c) {
 }
 
 constexpr size_t kLdsPerCu = 160 * 1024;      // gfx950
-int flush_pipeline(nhdfit_ctx* c);
-int refresh_layouts(nhdfit_ctx* c);
+
+// Argument blocks of the mapping roles for buffer set b of pipe p and a batch of P pods (shared by the step launch and the
+// single-launch finds), and the static tables of the kernels that map and commit on their own.
+MapArgs make_map_args(nhdfit_ctx* c, Pipe& p, int b, uint32_t P) {
+    MapArgs m;
+    memset(&m, 0, sizeof m);
+    m.p0 = c->p0.p; m.p1 = c->p1.p; m.p2 = c->p2.p; m.p3 = c->p3.p; m.det = c->det.p;
+    m.tabs = p.tabs[b].p; m.pitch = c->pitch; m.tile_wcls = c->tile_wcls.p;
+    for (int w = 0; w < kWClasses; ++w) m.L[w] = cold_view(c->L[w]);
+    m.n = c->n; m.global_base = c->global_base; m.reqs = c->reqs.p; m.P = P;
+    m.score = p.score[b].p; m.caps = c->caps.p; m.out = p.maps[b].p;
+    return m;
+}
+ShapeArgs make_shape_args(nhdfit_ctx* c, Pipe& p, int b) {
+    return ShapeArgs{p.shape_keys[b].p, p.shape_res[b].p, p.shape_slot[b].p, p.shape_list[b].p, c->asc.p, c->choose_tab.p,
+                     SetStates{c->st_info.p, c->st_next.p, c->st_asc.p, c->st_n}};
+}
+MapTables map_tables(nhdfit_ctx* c) {
+    return MapTables{c->asc.p, c->choose_tab.p, SetStates{c->st_info.p, c->st_next.p, c->st_asc.p, c->st_n}};
+}
+SigTable sig_table(nhdfit_ctx* c) { return SigTable{c->sig_keys.p, c->sig_ids.p, c->sig_mask}; }
+
+// The mapping phases of the staged batch's steps that have not all run, launched behind them.
+int flush_pipeline(nhdfit_ctx* c) {
+    if (!c->P || !c->want_map || c->n_big_pods >= c->P) return NHDFIT_OK;
+    const uint32_t tiles = (c->P + kTile - 1) / kTile;
+    for (Pipe& p : c->pipe) {
+        // the steps whose mapping phases have not all run: mapped from their scores in one launch (k_map_tiles, step_map.h)
+        while (p.n_finished < p.n_fit) {
+            DrainArgs a;
+            memset(&a, 0, sizeof a);
+            a.tiles = tiles;
+            a.h = make_shape_args(c, p, 0);
+            while (a.nsteps < (uint32_t)kDrainSteps && p.n_finished + a.nsteps < p.n_fit) {
+                const int b = (int)((p.n_finished + a.nsteps) % kBufs);
+                if (c->comm) HIPCHK(c, hipStreamWaitEvent(c->streams.use(p.k), p.ev_red[b], 0));      // the step's scores are final behind its all-reduce
+                a.m[a.nsteps++] = make_map_args(c, p, b, c->P);
+            }
+            const bool drain_prof = tune_env("NHDFIT_DRAIN_PROF") != nullptr;      // tuning aid: where a drain launch's time goes
+            if (drain_prof) {
+                HIPCHK(c, c->role_clock.reserve(16));
+                unsigned long long init[16] = {0};
+                init[7] = ~0ull;
+                HIPCHK(c, hipMemcpyAsync(c->role_clock.p, init, sizeof init, hipMemcpyHostToDevice, c->streams.use(p.k)));
+                a.clk = c->role_clock.p;
+            }
+            hipLaunchKernelGGL(k_map_tiles, dim3(a.nsteps * tiles), dim3(256), map_tile_lds_bytes<256>(), c->streams.use(p.k), a);
+            HIPCHK(c, hipGetLastError());
+            if (drain_prof) {
+                unsigned long long t[16];
+                HIPCHK(c, c->streams.wait(p.k));
+                HIPCHK(c, hipMemcpy(t, c->role_clock.p, sizeof t, hipMemcpyDeviceToHost));
+                fprintf(stderr, "[nhdfit] drain of %u step(s) x %u tiles: staged +%.2f, NIC bits / masks / key +%.2f, shapes de-duplicated +%.2f, state machine +%.2f, "
+                                "generic shapes +%.2f, finish +%.2f us after a block's start (latest block each); first block start to last block end %.2f us\n",
+                        a.nsteps, tiles, t[0] * 0.01, t[1] * 0.01, t[2] * 0.01, t[3] * 0.01, t[4] * 0.01, t[5] * 0.01, (t[6] - t[7]) * 0.01);
+            }
+            p.n_finished += a.nsteps;
+        }
+        p.n_shaped = p.n_chosen = p.n_finished;
+    }
+    return NHDFIT_OK;
+}
 
 // Tuning build only: where a shortcut skips the wait for a pipe other than the first or for the reduce stream because the ledger holds
 // no mark for it, the runtime is asked after all, and the call fails if the stream is not idle - every run of the GPU tests against
@@ -424,6 +506,25 @@ void reset_step_counters(nhdfit_ctx* c) {
     for (Pipe& p : c->pipe) p.n_dig = p.n_fit = p.n_shaped = p.n_chosen = p.n_finished = 0;
     c->n_enq = 0;
     c->last_pipe = 0;
+}
+
+// The staged batch ends here: nothing is staged for nhdfit_enqueue_step / nhdfit_fetch until stage_requests runs again.  The
+// single-launch forms pass their own batch size to the helpers, so no exit of theirs has c->P to put back.
+void end_staged_batch(nhdfit_ctx* c) {
+    reset_step_counters(c);
+    c->n_items = 0; c->n_big_pods = 0;
+    c->P = 0;
+}
+
+// The writer's rule, for a launch on pipe 0 that writes the planes of the mirror.  Steps in flight on EITHER pipe (their fit roles,
+// digests running ahead, pending mapping phases) read them: wait for every stream, as every other writer of the mirror does
+// (nhdfit_upload_nodes) ... unless nothing can be in flight anywhere but on that very stream: no batch is staged (the single-launch
+// finds leave none) and the ledger holds no mark for another pipe's stream or for the reduce stream - then stream order is all the
+// writer needs (the scheduler's pod-at-a-time loop: asking the stream whether the find's launch has retired cost ~10 us per pod).
+int writers_wait(nhdfit_ctx* c, const char* entry, bool* waited = nullptr) {
+    const bool wait = c->P || !c->streams.sides_clean();
+    if (waited) *waited = wait;
+    return wait ? sync_all(c) : check_skipped_waits(c, entry);
 }
 
 // The sequence number the next single-launch call stores behind its results (never 0, never kFindAborted).
@@ -483,6 +584,31 @@ int report_role_clock(nhdfit_ctx* c, int k, int slots, const char* line) {
         if (t[2 * s + 1]) fprintf(stderr, line, kRoleNames[s], (t[2 * s] - first) * 0.01, (t[2 * s + 1] - first) * 0.01);
     return NHDFIT_OK;
 }
+// ... around a single-launch call on pipe 0, of which every one is clocked: `words` is what the launch's arguments get (null: off);
+// the report's first line is `head` (which prints `blocks`) and when the host saw the results.
+int arm_launch_clock(nhdfit_ctx* c, int slots, unsigned long long*& words) {
+    words = nullptr;
+    if (kTuning && c->role_step >= 0) { TRY(arm_role_clock(c, 0, slots)); words = c->role_clock.p; }
+    return NHDFIT_OK;
+}
+int report_launch_clock(nhdfit_ctx* c, int slots, const char* head, uint32_t blocks, std::chrono::steady_clock::time_point t0,
+                        std::chrono::steady_clock::time_point t_launch) {
+    const double us_seen = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_launch).count();
+    fprintf(stderr, head, blocks);
+    fprintf(stderr, ", results seen %.1f us after the launch call began (host prep %.1f us)\n", us_seen, std::chrono::duration<double, std::micro>(t_launch - t0).count());
+    return report_role_clock(c, 0, slots, "[nhdfit]   %-6s: +%.2f us .. +%.2f us\n");
+}
+
+// Dynamic LDS of a launch's fit role: the staged table rows and the winner scratch of its nw wavefronts.
+size_t fit_launch_lds(const nhdfit_ctx* c, uint32_t nw) { return lds_slice(c->lds_bytes) + (size_t)nw * 64 * sizeof(unsigned long long); }
+
+// A single-launch find gave up on a wait (kFindAborted): its counters and its word go back to rest; the caller takes the staged path.
+int recover_abandoned_launch(nhdfit_ctx* c, uint32_t* sync, uint32_t words, uint32_t* flag) {
+    HIPCHK(c, c->streams.wait(0));
+    HIPCHK(c, hipMemsetAsync(sync, 0, (size_t)words * sizeof(uint32_t), c->streams.use(0)));
+    *flag = 0;
+    return NHDFIT_OK;
+}
 
 }  // namespace
 
@@ -498,7 +624,27 @@ int nhdfit_device_count(void) {
 
 const char* nhdfit_last_error(nhdfit_ctx* ctx) { return ctx ? ctx->err.c_str() : g_create_error.c_str(); }
 
-void nhdfit_destroy(nhdfit_ctx* c);
+void nhdfit_destroy(nhdfit_ctx* c) {
+    if (!c) return;
+    (void)hipSetDevice(c->dev);
+    (void)hipDeviceSynchronize();
+    if (c->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(c->comm);
+    if (c->find_host) (void)hipHostFree(c->find_host);              // the hipHostMalloc blocks that are no PinBuf
+    if (c->commit_host) (void)hipHostFree(c->commit_host);
+    if (c->findn_host) (void)hipHostFree(c->findn_host);
+    for (Pipe& p : c->pipe) {
+        for (int b = 0; b < kBufs; ++b) {
+            if (p.ev_fit[b]) (void)hipEventDestroy(p.ev_fit[b]);
+            if (p.ev_red[b]) (void)hipEventDestroy(p.ev_red[b]);
+        }
+        if (p.ev_staged) (void)hipEventDestroy(p.ev_staged);
+    }
+    for (auto& q : c->ev)
+        for (auto& x : q)
+            if (x) (void)hipEventDestroy(x);
+    c->streams.destroy();
+    delete c;                    // every DevBuf / PinBuf frees itself: the device is current, nothing is in flight
+}
 
 int nhdfit_create(int device_id, nhdfit_ctx** out) {
     if (!out) return fail(nullptr, NHDFIT_E_INVAL, "out is NULL");
@@ -578,28 +724,6 @@ int nhdfit_create(int device_id, nhdfit_ctx** out) {
     }
     *out = c;
     return NHDFIT_OK;
-}
-
-void nhdfit_destroy(nhdfit_ctx* c) {
-    if (!c) return;
-    (void)hipSetDevice(c->dev);
-    (void)hipDeviceSynchronize();
-    if (c->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(c->comm);
-    if (c->find_host) (void)hipHostFree(c->find_host);              // the hipHostMalloc blocks that are no PinBuf
-    if (c->commit_host) (void)hipHostFree(c->commit_host);
-    if (c->findn_host) (void)hipHostFree(c->findn_host);
-    for (Pipe& p : c->pipe) {
-        for (int b = 0; b < kBufs; ++b) {
-            if (p.ev_fit[b]) (void)hipEventDestroy(p.ev_fit[b]);
-            if (p.ev_red[b]) (void)hipEventDestroy(p.ev_red[b]);
-        }
-        if (p.ev_staged) (void)hipEventDestroy(p.ev_staged);
-    }
-    for (auto& q : c->ev)
-        for (auto& x : q)
-            if (x) (void)hipEventDestroy(x);
-    c->streams.destroy();
-    delete c;                    // every DevBuf / PinBuf frees itself: the device is current, nothing is in flight
 }
 
 int nhdfit_set_dictionary(nhdfit_ctx* c, uint32_t max_cores_per_numa, uint32_t max_gpus_per_numa,
@@ -773,8 +897,8 @@ int nhdfit_upload_nodes(nhdfit_ctx* c, uint32_t first, uint32_t count, const nhd
 }
 
 namespace {
-// Tile-image layouts for the current dictionary, staged batch and provisioned X rows; (re)sizes the image buffers.
-int refresh_layouts(nhdfit_ctx* c) {
+// Tile-image layouts for the current dictionary, a batch of P pods and the provisioned X rows; (re)sizes the image buffers for P pods.
+int refresh_layouts(nhdfit_ctx* c, uint32_t P) {
     uint32_t pitch = 0, hot = 0;
     for (uint32_t w = 0; w < (uint32_t)kWClasses; ++w) {
         c->L[w] = make_layout(2u << w, c->max_cores, c->max_gpus, c->nsig, c->ngs, c->hp_rows, c->x_cap);
@@ -822,16 +946,14 @@ int refresh_layouts(nhdfit_ctx* c) {
     c->pitch = pitch;
     c->lds_bytes = lds;
     c->x_spill = spill;
-    if (c->P) {
-        const uint32_t tiles = (c->P + kTile - 1) / kTile;
+    if (P) {
+        const uint32_t tiles = (P + kTile - 1) / kTile;
         for (Pipe& p : c->pipe)
             for (int b = 0; b < kBufs; ++b) HIPCHK(c, p.tabs[b].reserve((size_t)tiles * pitch));
     }
     return NHDFIT_OK;
 }
-}  // namespace
 
-namespace {
 // The order a call's pods are staged in (perm[k] = caller's index of the pod at device position k): a function of the requests
 // alone.  It is also the order in which EVERY form of a sharded find hands its score words to the all-reduce - the staged step and
 // the single-launch find alike - so that ranks that take different forms for the same call (one shard holds a wide node, spilled
@@ -859,14 +981,11 @@ void staged_order(const nhdfit_req* reqs, uint32_t P, std::vector<uint32_t>& per
     for (uint32_t p = 0; p < P; ++p) perm[start[key[p]]++] = p;
     if (seen) *seen = sn;
 }
-}  // namespace
 
-namespace {
 // What the staging leaves in page-locked host memory goes to the device by copy commands - one per array, and every command costs the
 // copy engine ~10 us before its first byte moves.  The single-launch find of a batch reads the small arrays (tile classes, work items)
 // straight from the host block and, for a batch of a few tiles, the request records too; the copies it skipped are made up for here
 // when the call takes the steps' path after all.
-int stage_requests(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, bool defer_small_copies, bool defer_request_copy, size_t tail_bytes = 0);
 int finish_deferred_copies(nhdfit_ctx* c) {
     const uint32_t tiles = (c->P + kTile - 1) / kTile;
     if (c->reqs_deferred) HIPCHK(c, hipMemcpyAsync(c->reqs.p, c->pin_reqs.p, (size_t)c->P * sizeof(nhdfit_req), hipMemcpyHostToDevice, c->streams.use(0)));
@@ -874,15 +993,8 @@ int finish_deferred_copies(nhdfit_ctx* c) {
     c->reqs_deferred = c->wcls_deferred = false;
     return NHDFIT_OK;
 }
-}  // namespace
 
-int nhdfit_stage_requests(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P) {
-    if (!c) return NHDFIT_E_INVAL;
-    return stage_requests(c, reqs, P, false, false);
-}
-
-namespace {
-int stage_requests(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, bool defer_small_copies, bool defer_request_copy, size_t tail_bytes) {
+int stage_requests(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, bool defer_small_copies, bool defer_request_copy, size_t tail_bytes = 0) {
     if (!reqs || !P) return fail(c, NHDFIT_E_INVAL, "no requests");
     if (!c->nsig) return fail(c, NHDFIT_E_STATE, "set the dictionary first");
     PhaseTimer prof{"  stage", P};
@@ -960,7 +1072,7 @@ int stage_requests(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, bool defer
     c->n_items = 0;                                 // the fit role's work items are rebuilt at the next step
     c->use_cand = false;
     prof.lap("copies enqueued");
-    TRY(refresh_layouts(c));
+    TRY(refresh_layouts(c, P));
     prof.lap("layouts");
     // a node's C row depends on the pair table's dimension: a batch that changes it has the chunks' records dealt to the lanes again
     // (ensure_records, in front of the batch's first step) - a full tile and more only: smaller batches are latency, not throughput
@@ -970,9 +1082,8 @@ int stage_requests(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, bool defer
     if (P > (uint32_t)kTile && (c->pair_D[0] != c->crow_D[0] || c->pair_D[1] != c->crow_D[1])) c->crow_stale = true;
     return NHDFIT_OK;
 }
-}  // namespace
 
-static int stage_cand(nhdfit_ctx* c, const uint64_t* cand) {
+int stage_cand(nhdfit_ctx* c, const uint64_t* cand) {
     const size_t chunks = (c->n + 63) / 64;
     HIPCHK(c, c->cand.reserve(chunks ? chunks : 1));
     HIPCHK(c, hipMemcpy(c->cand.p, cand, chunks * sizeof(uint64_t), hipMemcpyHostToDevice));
@@ -980,8 +1091,6 @@ static int stage_cand(nhdfit_ctx* c, const uint64_t* cand) {
     c->use_cand = true;
     return NHDFIT_OK;
 }
-
-namespace {
 
 // `every`: all chunks, for the pair-table dimensions of the staged batch (they become order_D); otherwise the chunks k_xrecords just
 // rewrote, for the dimensions the others were dealt for
@@ -1001,7 +1110,7 @@ int order_chunks(nhdfit_ctx* c, uint32_t first_chunk, uint32_t n_chunks, bool ev
 // Bring the node records (and the class table behind their X rows) up to date with the mirror.  Cheap no-op when
 // nothing changed; otherwise three small kernels over the touched nodes and one 8-byte read-back (the host sizes the
 // tile images by the class count).  A grown class count or a changed dictionary re-does every record.
-int ensure_records(nhdfit_ctx* c) {
+int ensure_records(nhdfit_ctx* c, uint32_t P) {
     const uint32_t all_chunks = (c->n + 63) / 64;
     // dealing the records to the lanes pays where the fit role is more than a launch: from 128 chunks on
     const bool deal = all_chunks >= 128;
@@ -1084,7 +1193,7 @@ int ensure_records(nhdfit_ctx* c) {
         c->x_cap = x_capacity(nx[0]);
         c->rec_all = true;
         for (Pipe& p : c->pipe) p.n_dig = std::min(p.n_dig, p.n_fit);   // every staged table image is redone
-        TRY(refresh_layouts(c));
+        TRY(refresh_layouts(c, P));
     }
     if (deal) {
         // a few rewritten chunks (the scheduler's loop: one commit, then the next find) stay in node order until the next full deal -
@@ -1161,23 +1270,9 @@ int build_items(nhdfit_ctx* c, uint32_t nw, bool batch_find = false) {
     return NHDFIT_OK;
 }
 
-// Argument blocks of the roles for buffer set b of pipe p (shared by the step launch and the single-launch find).
-MapArgs make_map_args(nhdfit_ctx* c, Pipe& p, int b) {
-    MapArgs m;
-    memset(&m, 0, sizeof m);
-    m.p0 = c->p0.p; m.p1 = c->p1.p; m.p2 = c->p2.p; m.p3 = c->p3.p; m.det = c->det.p;
-    m.tabs = p.tabs[b].p; m.pitch = c->pitch; m.tile_wcls = c->tile_wcls.p;
-    for (int w = 0; w < kWClasses; ++w) m.L[w] = cold_view(c->L[w]);
-    m.n = c->n; m.global_base = c->global_base; m.reqs = c->reqs.p; m.P = c->P;
-    m.score = p.score[b].p; m.caps = c->caps.p; m.out = p.maps[b].p;
-    return m;
-}
-ShapeArgs make_shape_args(nhdfit_ctx* c, Pipe& p, int b) {
-    return ShapeArgs{p.shape_keys[b].p, p.shape_res[b].p, p.shape_slot[b].p, p.shape_list[b].p, c->asc.p, c->choose_tab.p,
-                     SetStates{c->st_info.p, c->st_next.p, c->st_asc.p, c->st_n}};
-}
-void fill_digest_args(nhdfit_ctx* c, Pipe& p, int b, uint32_t wc_parts, DigestArgs& d) {
-    d.reqs = c->reqs.p; d.P = c->P;
+// Argument blocks of the digest and fit roles for buffer set b of pipe p and a batch of P pods (the mapping roles': make_map_args).
+void fill_digest_args(nhdfit_ctx* c, Pipe& p, int b, uint32_t wc_parts, uint32_t P, DigestArgs& d) {
+    d.reqs = c->reqs.p; d.P = P;
     d.d = DictView{c->caps.p, c->ncls, c->group_sets.p, SigDict{c->sig_off.p, c->pool_off.p, c->pool_glimit.p, c->cc.p, c->nsig}, c->sig_flat.p, c->flat_words,
                    c->sig_flat2.p, c->flat2_words};
     for (int w = 0; w < kWClasses; ++w) d.L[w] = c->L[w];
@@ -1192,7 +1287,7 @@ void fill_digest_args(nhdfit_ctx* c, Pipe& p, int b, uint32_t wc_parts, DigestAr
     d.n_sig_list = listed ? c->n_sig_use : 0;
     d.count = p.dig_count.p;
 }
-void fill_fit_args(nhdfit_ctx* c, Pipe& p, int bf, double now, FitArgs& f, bool pair = false) {
+void fill_fit_args(nhdfit_ctx* c, Pipe& p, int bf, double now, uint32_t P, FitArgs& f, bool pair = false) {
     for (int w = 0; w < 2; ++w) {
         f.pair_D[w] = pair ? c->pair_D[w] : 0u;
         f.crow_ok[w] = pair && c->pair_D[w] != 0u && c->crow_D[w] == c->pair_D[w] && !c->crow_stale ? 1u : 0u;
@@ -1204,7 +1299,7 @@ void fill_fit_args(nhdfit_ctx* c, Pipe& p, int bf, double now, FitArgs& f, bool 
     }
     f.hp_last = c->hp_rows - 1; f.hp_bytes = align16(c->hp_rows * 8);
     f.n = c->n; f.chunks = (c->n + 63) / 64; f.global_base = c->global_base; f.busy_from = busy_threshold(now);
-    f.tabs = p.tabs[bf].p; f.pitch = c->pitch; f.hdr = p.hdr[bf].p; f.P = c->P;
+    f.tabs = p.tabs[bf].p; f.pitch = c->pitch; f.hdr = p.hdr[bf].p; f.P = P;
     f.cand = c->use_cand ? c->cand.p : nullptr;
     f.nm = c->want_bitmap ? p.nm.p : nullptr;
     f.score = p.score[bf].p;
@@ -1221,7 +1316,7 @@ int launch_step(nhdfit_ctx* c, Pipe& p, bool with_fit, bool with_digest, double 
     const bool big = c->geom_big;
     const uint32_t block = big ? 512 : 256, nw = block / 64;
     const bool small_map = c->want_map && c->n_big_pods < P;
-    if (with_fit || with_digest) TRY(ensure_records(c));
+    if (with_fit || with_digest) TRY(ensure_records(c, P));
     if (with_fit && !c->n_items) TRY(build_items(c, nw));
     if (&p != &c->pipe[0] && p.seen_gen != c->staged_gen) {
         // what pipe 0's stream staged since this pipe last looked (requests, work items, node records) is in front of this launch
@@ -1234,17 +1329,15 @@ int launch_step(nhdfit_ctx* c, Pipe& p, bool with_fit, bool with_digest, double 
     memset(&a, 0, sizeof a);
     a.shapes_P = P;
     a.side_prio = 1;                                            // the side roles issue ahead of the fit role's wavefronts (settled in round 2)
-    auto map_args = [&](int b) { return make_map_args(c, p, b); };
-    auto shape_args = [&](int b) { return make_shape_args(c, p, b); };
     // mapping phases of earlier steps: each advances by at most one step per launch
     bool did_shapes = false, did_choose = false, did_finish = false;
     if (small_map) {
         if (p.n_finished < p.n_chosen) {
             const int b = (int)(p.n_finished % kBufs);
-            a.finish_m = map_args(b); a.finish_h = shape_args(b); a.nb_finish = (P + block / 4 - 1) / (block / 4); did_finish = true;
+            a.finish_m = make_map_args(c, p, b, P); a.finish_h = make_shape_args(c, p, b); a.nb_finish = (P + block / 4 - 1) / (block / 4); did_finish = true;
         }
         if (p.n_chosen < p.n_shaped) {
-            a.choose = shape_args((int)(p.n_chosen % kBufs));
+            a.choose = make_shape_args(c, p, (int)(p.n_chosen % kBufs));
             a.choose_lanes = 1u;                                // wavefront = tile, lane = shape: a wavefront per shape took 16 x the blocks (round 2)
             a.nb_choose = (tiles + nw - 1) / nw; did_choose = true;
         }
@@ -1258,7 +1351,7 @@ int launch_step(nhdfit_ctx* c, Pipe& p, bool with_fit, bool with_digest, double 
             HIPCHK(c, p.shape_res[b].reserve((size_t)tiles * kTile));
             HIPCHK(c, p.shape_slot[b].reserve(P));
             HIPCHK(c, p.shape_list[b].reserve(tiles));
-            a.shapes_m = map_args(b); a.shapes_h = shape_args(b); a.nb_shapes = (P + block / 4 - 1) / (block / 4); did_shapes = true;
+            a.shapes_m = make_map_args(c, p, b, P); a.shapes_h = make_shape_args(c, p, b); a.nb_shapes = (P + block / 4 - 1) / (block / 4); did_shapes = true;
         }
     }
     with_digest = with_digest && p.n_dig <= p.n_fit + (with_fit ? 1 : 0);   // at most one step ahead of the fit
@@ -1268,7 +1361,7 @@ int launch_step(nhdfit_ctx* c, Pipe& p, bool with_fit, bool with_digest, double 
         // two blocks per tile for the CPU rows, not the four of the single-launch finds: the digest's latency hides behind the other
         // pipes' launches, its block slots do not (-3 %, profiles/r03)
         constexpr uint32_t wc_parts = 2;
-        fill_digest_args(c, p, b, wc_parts, d);
+        fill_digest_args(c, p, b, wc_parts, P, d);
         a.nb_digest = tiles * (1u + wc_parts);
     }
     uint32_t nb_fit = 0;
@@ -1276,14 +1369,14 @@ int launch_step(nhdfit_ctx* c, Pipe& p, bool with_fit, bool with_digest, double 
     if (with_fit) {
         bf = (int)(p.n_fit % kBufs);
         if (c->want_bitmap) HIPCHK(c, p.nm.reserve((size_t)tiles * chunks * 64));
-        fill_fit_args(c, p, bf, now, a.fit, !c->x_spill);      // (pair tables wherever the class rows do not spill)
+        fill_fit_args(c, p, bf, now, P, a.fit, !c->x_spill);      // (pair tables wherever the class rows do not spill)
         nb_fit = c->n_items;
     }
     a.nb_fit = nb_fit;
     const uint32_t grid = a.nb_choose + a.nb_shapes + a.nb_finish + a.nb_digest + nb_fit;
     if (!grid) return NHDFIT_OK;
     // dynamic LDS of the launch: the largest need among the roles present
-    size_t lds = nb_fit ? lds_slice(c->lds_bytes) + (size_t)nw * 64 * sizeof(unsigned long long) : 0;
+    size_t lds = nb_fit ? fit_launch_lds(c, nw) : 0;
     if (a.nb_digest && kDigestLds > lds) lds = kDigestLds;
     const size_t map_lds = big ? map_lds_bytes<512>() : map_lds_bytes<256>();
     if ((a.nb_shapes || a.nb_finish) && map_lds > lds) lds = map_lds;
@@ -1344,7 +1437,7 @@ int launch_step(nhdfit_ctx* c, Pipe& p, bool with_fit, bool with_digest, double 
         }
         if (c->want_map && c->n_big_pods) {      // pods with 4 proc groups: generic set model (scratch-heavy, kept out of k_step)
             const dim3 mg((P + kMapWaves - 1) / kMapWaves), mb(64 * kMapWaves);
-            hipLaunchKernelGGL(k_map<true>, mg, mb, 0, c->streams.use(after), map_args(bf));
+            hipLaunchKernelGGL(k_map<true>, mg, mb, 0, c->streams.use(after), make_map_args(c, p, bf, P));
             HIPCHK(c, hipGetLastError());
         }
         if (c->comm) HIPCHK(c, hipEventRecord(p.ev_red[bf], c->streams.use(kRed)));
@@ -1371,73 +1464,7 @@ int convert_rows(nhdfit_ctx* c, Pipe& p) {
     return NHDFIT_OK;
 }
 
-// the sequential kernels' copy, [P][chunks]; stream order is all they need
-int convert_rows_t(nhdfit_ctx* c, Pipe& p) {
-    const uint32_t chunks = (c->n + 63) / 64, tiles = (c->P + kTile - 1) / kTile;
-    const uint32_t groups = (chunks + kRowsTChunks - 1) / kRowsTChunks;
-    HIPCHK(c, c->rows_t.reserve((size_t)chunks * c->P));
-    hipLaunchKernelGGL(k_rows_t, dim3((tiles * groups + 3) / 4), dim3(256), 0, c->streams.use(p.k), p.nm.p, c->rows_t.p, chunks, c->P);
-    HIPCHK(c, hipGetLastError());
-    return NHDFIT_OK;
-}
-
-int flush_pipeline(nhdfit_ctx* c) {
-    if (!c->P || !c->want_map || c->n_big_pods >= c->P) return NHDFIT_OK;
-    const uint32_t tiles = (c->P + kTile - 1) / kTile;
-    for (Pipe& p : c->pipe) {
-        // the steps whose mapping phases have not all run: mapped from their scores in one launch (k_map_tiles, step_map.h)
-        while (p.n_finished < p.n_fit) {
-            DrainArgs a;
-            memset(&a, 0, sizeof a);
-            a.tiles = tiles;
-            a.h = make_shape_args(c, p, 0);
-            while (a.nsteps < (uint32_t)kDrainSteps && p.n_finished + a.nsteps < p.n_fit) {
-                const int b = (int)((p.n_finished + a.nsteps) % kBufs);
-                if (c->comm) HIPCHK(c, hipStreamWaitEvent(c->streams.use(p.k), p.ev_red[b], 0));      // the step's scores are final behind its all-reduce
-                a.m[a.nsteps++] = make_map_args(c, p, b);
-            }
-            const bool drain_prof = tune_env("NHDFIT_DRAIN_PROF") != nullptr;      // tuning aid: where a drain launch's time goes
-            if (drain_prof) {
-                HIPCHK(c, c->role_clock.reserve(16));
-                unsigned long long init[16] = {0};
-                init[7] = ~0ull;
-                HIPCHK(c, hipMemcpyAsync(c->role_clock.p, init, sizeof init, hipMemcpyHostToDevice, c->streams.use(p.k)));
-                a.clk = c->role_clock.p;
-            }
-            hipLaunchKernelGGL(k_map_tiles, dim3(a.nsteps * tiles), dim3(256), map_tile_lds_bytes<256>(), c->streams.use(p.k), a);
-            HIPCHK(c, hipGetLastError());
-            if (drain_prof) {
-                unsigned long long t[16];
-                HIPCHK(c, c->streams.wait(p.k));
-                HIPCHK(c, hipMemcpy(t, c->role_clock.p, sizeof t, hipMemcpyDeviceToHost));
-                fprintf(stderr, "[nhdfit] drain of %u step(s) x %u tiles: staged +%.2f, NIC bits / masks / key +%.2f, shapes de-duplicated +%.2f, state machine +%.2f, "
-                                "generic shapes +%.2f, finish +%.2f us after a block's start (latest block each); first block start to last block end %.2f us\n",
-                        a.nsteps, tiles, t[0] * 0.01, t[1] * 0.01, t[2] * 0.01, t[3] * 0.01, t[4] * 0.01, t[5] * 0.01, (t[6] - t[7]) * 0.01);
-            }
-            p.n_finished += a.nsteps;
-        }
-        p.n_shaped = p.n_chosen = p.n_finished;
-    }
-    return NHDFIT_OK;
-}
-
-}  // namespace
-
-static int enqueue_step(nhdfit_ctx* c, double now);
-int nhdfit_enqueue_step(nhdfit_ctx* c, double now) {
-    if (!c) return NHDFIT_E_INVAL;
-    static const bool enq_prof = tune_env("NHDFIT_ENQ_PROF") != nullptr;
-    if (!enq_prof) return enqueue_step(c, now);
-    const auto t0 = std::chrono::steady_clock::now();
-    const int rc = enqueue_step(c, now);
-    c->enq_us += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
-    if (++c->enq_n % 1000 == 0) {
-        fprintf(stderr, "[nhdfit] 1000 enqueues: %.2f us each on the host, %.2f in the launch calls, %.2f in event records\n", c->enq_us / 1000, c->enq_launch_us / 1000, c->enq_events_us / 1000);
-        c->enq_us = c->enq_launch_us = c->enq_events_us = 0;
-    }
-    return rc;
-}
-static int enqueue_step(nhdfit_ctx* c, double now) {
+int enqueue_step(nhdfit_ctx* c, double now) {
     if (!c->P) return fail(c, NHDFIT_E_STATE, "stage requests first");
     if (!c->n) return fail(c, NHDFIT_E_STATE, "no nodes uploaded");
     HIPCHK(c, hipSetDevice(c->dev));
@@ -1462,11 +1489,32 @@ static int enqueue_step(nhdfit_ctx* c, double now) {
     c->last_pipe = which;
     // the mirror may have changed since the last step (uploads, commits, deltas between two steps of one staged batch): node
     // records first - new node classes put the digests that ran ahead back (ensure_records), and they are redone below
-    TRY(ensure_records(c));
+    TRY(ensure_records(c, c->P));
     if (p.n_dig <= p.n_fit) {                        // this pipe's first step after staging (or after such a change): its digest has not run yet
         TRY(launch_step(c, p, false, true, now));
     }
     return launch_step(c, p, true, true, now);
+}
+
+}  // namespace
+
+int nhdfit_stage_requests(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P) {
+    if (!c) return NHDFIT_E_INVAL;
+    return stage_requests(c, reqs, P, false, false);
+}
+
+int nhdfit_enqueue_step(nhdfit_ctx* c, double now) {
+    if (!c) return NHDFIT_E_INVAL;
+    static const bool enq_prof = tune_env("NHDFIT_ENQ_PROF") != nullptr;
+    if (!enq_prof) return enqueue_step(c, now);
+    const auto t0 = std::chrono::steady_clock::now();
+    const int rc = enqueue_step(c, now);
+    c->enq_us += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+    if (++c->enq_n % 1000 == 0) {
+        fprintf(stderr, "[nhdfit] 1000 enqueues: %.2f us each on the host, %.2f in the launch calls, %.2f in event records\n", c->enq_us / 1000, c->enq_launch_us / 1000, c->enq_events_us / 1000);
+        c->enq_us = c->enq_launch_us = c->enq_events_us = 0;
+    }
+    return rc;
 }
 
 int nhdfit_sync(nhdfit_ctx* c) {
@@ -1539,8 +1587,8 @@ Find1Args lone_find_args(nhdfit_ctx* c, double now, uint32_t seq, bool want_map)
     const uint32_t chunks = (c->n + 63) / 64;
     Find1Args a1;
     memset(&a1, 0, sizeof a1);
-    a1.m = make_map_args(c, p, 0);
-    a1.m.reqs = h->reqs; a1.m.tile_wcls = nullptr; a1.m.tabs = nullptr; a1.m.out = h->maps; a1.m.P = 1;
+    a1.m = make_map_args(c, p, 0, 1);
+    a1.m.reqs = h->reqs; a1.m.tile_wcls = nullptr; a1.m.tabs = nullptr; a1.m.out = h->maps;
     a1.m.score = reinterpret_cast<const unsigned long long*>(c->find_sync.p + 4);
     a1.h = make_shape_args(c, p, 0);
     a1.p4 = c->p4.p;
@@ -1567,6 +1615,15 @@ hipError_t upload_small_cand(nhdfit_ctx* c, const uint64_t* cand) {
     }
     return e;
 }
+// The lone-pod rule, asked by nhdfit_find's one-pod form and by nhdfit_find_commit's fused form: whether one request can take the
+// table-free launch (k_find1, k_find1_commit) - what every single-launch find asks (ordinary nodes only, no four-group pod: the generic
+// set model is a kernel of its own), and the dictionary's 16-bit stream and its signature count within the block's LDS.
+bool lone_pod_form(const nhdfit_ctx* c, const nhdfit_req& r) {
+    if (!c->fast_find || !c->lone_pod || !c->nsig || !c->n || !c->find_host || c->n_wide) return false;
+    if (r.hugepages_gb < 0 || r.hugepages_gb > kMaxHpRows - 2) return false;
+    if (req_valid(r) && r.n_groups > 3) return false;
+    return c->flat_words && c->flat_words <= kDictLdsWords && c->nsig <= kLoneMaxSigs;
+}
 // nhdfit_find for at most one pod tile and no verdict matrix - the scheduler's pod-at-a-time FindNode - as ONE launch (k_find,
 // step_kernel.h): the requests are read from, and the results stored into, a fine-grained host block; the host polls the
 // sequence word the launch stores last.  Returns 1 when the call is not eligible (or the launch gave up): the caller then
@@ -1591,74 +1648,60 @@ int find_small(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, double now, co
         TRY(drain_events(c));
     }
     Pipe& p = c->pipe[0];
-    reset_step_counters(c);
-    c->n_items = 0; c->n_big_pods = 0;
-    // one pod: no table image at all (k_find1) when the dictionary's 16-bit stream and its signature count fit the block's LDS
-    const bool lone = P == 1 && c->lone_pod && c->flat_words && c->flat_words <= kDictLdsWords && c->nsig <= kLoneMaxSigs;
-    c->P = P;                                                   // (for the layout / argument helpers; nothing stays staged: reset below)
+    end_staged_batch(c);                                        // nothing is, or stays, staged for nhdfit_enqueue_step / nhdfit_fetch
+    const bool lone = P == 1 && lone_pod_form(c, reqs[0]);      // one pod: no table image at all (k_find1)
     c->hp_rows = (uint32_t)hp_max + 2;
     c->max_wcls = wcls;
-    int rc = lone ? NHDFIT_OK : refresh_layouts(c);
-    if (!rc && !lone) rc = ensure_records(c);
-    if (rc || (!lone && c->x_spill)) { c->P = 0; return rc ? rc : 1; }
+    if (!lone) {
+        TRY(refresh_layouts(c, P));
+        TRY(ensure_records(c, P));
+        if (c->x_spill) return 1;
+    }
     hipError_t e = lone ? hipSuccess : p.hdr[0].reserve(kTile);
     if (e == hipSuccess) e = p.score[0].reserve(kTile);
     const uint32_t chunks = (c->n + 63) / 64;
-    c->use_cand = cand != nullptr;
     if (e == hipSuccess) e = upload_small_cand(c, cand);
-    if (e != hipSuccess) { c->P = 0; return fail(c, NHDFIT_E_HIP, "small find: %s", hipGetErrorString(e)); }
+    if (e != hipSuccess) return fail(c, NHDFIT_E_HIP, "small find: %s", hipGetErrorString(e));
 
     FindHost* h = c->find_host;
     memcpy(h->reqs, reqs, (size_t)P * sizeof *reqs);
     const uint32_t seq = next_find_seq(c);
-    Find1Args a1;
-    memset(&a1, 0, sizeof a1);
-    if (lone) a1 = lone_find_args(c, now, seq, map_out != nullptr);
+    Find1Args a1 = lone ? lone_find_args(c, now, seq, map_out != nullptr) : Find1Args{};
     FindArgs a;
     memset(&a, 0, sizeof a);
     a.s.shapes_P = P;
-    fill_digest_args(c, p, 0, kWcPartsDefault, a.s.digest);     // (the digest is on the call's critical path: the CPU rows cut four ways)
+    fill_digest_args(c, p, 0, kWcPartsDefault, P, a.s.digest);  // (the digest is on the call's critical path: the CPU rows cut four ways)
     a.s.digest.reqs = h->reqs;
     a.s.nb_digest = 1u + kWcPartsDefault;
-    fill_fit_args(c, p, 0, now, a.s.fit);
+    fill_fit_args(c, p, 0, now, P, a.s.fit);
     a.s.fit.nm = nullptr; a.s.fit.items = nullptr; a.s.fit.dbg_skip = 0;
     constexpr uint32_t nw = 4;                                  // 256-thread blocks: a wavefront per chunk where the cluster is small enough
     // Few, longer fit blocks: every block stages the tile's table rows (tens of KB) before its first chunk and waits for the digest
     // on one counter - measured at 65 536 nodes (profiles/r03): 256 blocks 107 us per call, 64 blocks 54, 32 blocks 50.  Eight
     // chunks per wavefront, at most one block per CU.
     a.s.nb_fit = std::max(1u, std::min((chunks + 8 * nw - 1) / (8 * nw), (uint32_t)c->prop.multiProcessorCount));
-    a.s.finish_m = make_map_args(c, p, 0);                      // the mapping tail (map_one_tile): requests in, mappings out of the host block
+    a.s.finish_m = make_map_args(c, p, 0, P);                   // the mapping tail (map_one_tile): requests in, mappings out of the host block
     a.s.finish_m.reqs = h->reqs; a.s.finish_m.tile_wcls = nullptr; a.s.finish_m.out = h->maps;
     a.s.finish_h = make_shape_args(c, p, 0);
     a.wcls = wcls; a.want_map = map_out ? 1u : 0u;
     a.sync = c->find_sync.p; a.host = h; a.seq = seq;
-    size_t lds = lds_slice(c->lds_bytes) + (size_t)nw * 64 * sizeof(unsigned long long);
-    lds = std::max(lds, std::max(kDigestLds, map_tile_lds_bytes<256>()));
-    const bool clocks = kTuning && c->role_step >= 0;           // tuning aid (NHDFIT_ROLE_TIMES): the phases of the launch on the device clock
-    if (clocks) {
-        TRY(arm_role_clock(c, 0, 5));
-        a.s.role_clock = c->role_clock.p;
-        a1.role_clock = c->role_clock.p;
-    }
+    const size_t lds = std::max(fit_launch_lds(c, nw), std::max(kDigestLds, map_tile_lds_bytes<256>()));
+    unsigned long long* clocks;                                 // tuning aid (NHDFIT_ROLE_TIMES): the phases of the launch on the device clock
+    TRY(arm_launch_clock(c, 5, clocks));
+    a.s.role_clock = a1.role_clock = clocks;
     const auto t_launch = std::chrono::steady_clock::now();
-    c->P = 0;                                                   // nothing is staged for nhdfit_enqueue_step / nhdfit_fetch
     if (lone) hipLaunchKernelGGL((k_find1<256>), dim3(a1.nb), dim3(256), kLoneLds + map_tile_lds_bytes<256>(), c->streams.use(0), a1);
     else hipLaunchKernelGGL((k_find<256>), dim3(a.s.nb_digest + a.s.nb_fit), dim3(256), lds, c->streams.use(0), a);
     HIPCHK(c, hipGetLastError());
     uint32_t seen = 0;
     TRY(poll_word(c, &h->flag, seq, kFindAborted, t_launch, 500, 0, seen));
-    if (seen != seq) {                                          // the launch gave up on a wait: counters back to zero, staged path
-        HIPCHK(c, c->streams.wait(0));
-        HIPCHK(c, hipMemsetAsync(c->find_sync.p, 0, 8 * sizeof(uint32_t), c->streams.use(0)));
-        h->flag = 0;
+    if (seen != seq) {                                          // the launch gave up on a wait: staged path
+        TRY(recover_abandoned_launch(c, c->find_sync.p, 8, &h->flag));
         return 1;
     }
-    if (clocks) {
-        const double us_seen = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_launch).count();
-        fprintf(stderr, "[nhdfit] single-launch find%s: %u fit blocks, results seen %.1f us after the launch call began (host prep %.1f us)\n", lone ? " (lone pod, no tables)" : "", lone ? a1.nb : a.s.nb_fit, us_seen,
-                std::chrono::duration<double, std::micro>(t_launch - t0).count());
-        TRY(report_role_clock(c, 0, 5, "[nhdfit]   %-6s: +%.2f us .. +%.2f us\n"));
-    }
+    if (clocks)
+        TRY(report_launch_clock(c, 5, lone ? "[nhdfit] single-launch find (lone pod, no tables): %u fit blocks" : "[nhdfit] single-launch find: %u fit blocks",
+                                lone ? a1.nb : a.s.nb_fit, t0, t_launch));
     if (c->comm) {
         // sharded: every rank ran the launch on its shard and mapped its own winner; one all-reduce(max) of the packed scores
         // (<= 64 words) picks the cluster's winner, and a rank that does not own it drops its mapping - exactly what the
@@ -1689,29 +1732,20 @@ int find_small(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, double now, co
     return NHDFIT_OK;
 }
 
-// nhdfit_find_commit as ONE launch (k_find1_commit, find1_commit.h) when the lone-pod form of the find applies: the conditions are the
-// ones find_small tests for a lone pod, and no communicator (the winner of a sharded find is known only behind the all-reduce).
+// nhdfit_find_commit as ONE launch (k_find1_commit, find1_commit.h) when the lone-pod form of the find applies (lone_pod_form), there
+// is no communicator (the winner of a sharded find is known only behind the all-reduce) and the mapping output is on.
 // Returns 0 = done; 1 = not eligible, nothing launched, nothing touched; 2 = launched, a node was found and mapped (score_out / map_out
 // are filled, the correction is in the mirror) but NOT committed - the caller finishes with nhdfit_commit; < 0 = error (worded).
-SigTable sig_table(nhdfit_ctx* c);
 int find_commit_fused(nhdfit_ctx* c, const nhdfit_req* req, double now, const uint64_t* cand, double busy_time, int64_t prev_node,
                       double prev_busy_time, uint64_t* score_out, nhdfit_mapping* map_out, nhdfit_placement* place_out, int* committed) {
-    if (!c->fast_find || !c->lone_pod || !c->nsig || !c->n || !c->find_host || c->n_wide || c->comm || !c->want_map) return 1;
-    if (req->hugepages_gb < 0 || req->hugepages_gb > kMaxHpRows - 2) return 1;
-    if (req_valid(*req) && req->n_groups > 3) return 1;         // the generic set model is a kernel of its own
-    if (!c->flat_words || c->flat_words > kDictLdsWords || c->nsig > kLoneMaxSigs) return 1;
+    if (!lone_pod_form(c, *req) || c->comm || !c->want_map) return 1;
     const auto t0 = std::chrono::steady_clock::now();
     HIPCHK(c, hipSetDevice(c->dev));
-    // the launch writes the planes: the writer's rule of nhdfit_commit - steps in flight on either pipe read them, so wait for every
-    // stream, unless nothing can be in flight anywhere but on this very stream
-    if (c->P || !c->streams.sides_clean()) {
-        TRY(sync_all(c));
-        TRY(drain_events(c));
-    } else TRY(check_skipped_waits(c, "nhdfit_find_commit"));
+    bool waited = false;                                        // the launch writes the planes
+    TRY(writers_wait(c, "nhdfit_find_commit", &waited));
+    if (waited) TRY(drain_events(c));
     Pipe& p = c->pipe[0];
-    reset_step_counters(c);
-    c->n_items = 0; c->n_big_pods = 0;
-    c->P = 0;                                                   // nothing is (or stays) staged
+    end_staged_batch(c);                                        // nothing is, or stays, staged
     c->hp_rows = (uint32_t)req->hugepages_gb + 2;
     c->max_wcls = req_valid(*req) ? wclass_of(req->n_groups) : 0;
     hipError_t e = p.score[0].reserve(kTile);
@@ -1728,24 +1762,15 @@ int find_commit_fused(nhdfit_ctx* c, const nhdfit_req* req, double now, const ui
     a.sigs = sig_table(c); a.ncls = c->ncls;
     a.busy_time = busy_time;
     a.prev_node = prev_node < 0 ? kNoPrevNode : (uint32_t)prev_node; a.prev_busy_time = prev_busy_time;
-    const bool clocks = kTuning && c->role_step >= 0;           // tuning aid (NHDFIT_ROLE_TIMES): the phases of the launch on the device clock
     constexpr int kSlots = kClockCommitTail + 1;                // (the five roles' slots and the commit's)
-    if (clocks) {
-        TRY(arm_role_clock(c, 0, kSlots));
-        a.f.role_clock = c->role_clock.p;
-    }
+    TRY(arm_launch_clock(c, kSlots, a.f.role_clock));           // tuning aid (NHDFIT_ROLE_TIMES): the phases of the launch on the device clock
     const auto t_launch = std::chrono::steady_clock::now();
     hipLaunchKernelGGL((k_find1_commit<256>), dim3(a.f.nb), dim3(256), kLoneLds + map_tile_lds_bytes<256>(), c->streams.use(0), a);
     HIPCHK(c, hipGetLastError());
     uint32_t seen = 0;
     TRY(poll_word(c, &h->flag, seq, seq, t_launch, 500, 0, seen));
     if (seen != seq) return fail(c, NHDFIT_E_HIP, "the find-and-commit kernel ended without publishing its results");
-    if (clocks) {
-        const double us_seen = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_launch).count();
-        fprintf(stderr, "[nhdfit] find and commit in one launch: %u blocks, results seen %.1f us after the launch call began (host prep %.1f us)\n", a.f.nb, us_seen,
-                std::chrono::duration<double, std::micro>(t_launch - t0).count());
-        TRY(report_role_clock(c, 0, kSlots, "[nhdfit]   %-6s: +%.2f us .. +%.2f us\n"));
-    }
+    if (a.f.role_clock) TRY(report_launch_clock(c, kSlots, "[nhdfit] find and commit in one launch: %u blocks", a.f.nb, t0, t_launch));
     *score_out = h->score[0];
     *map_out = h->maps[0];
     store_find_stats(c, c->n, (uint64_t)c->n * 24ull + sizeof(nhdfit_req) + 8ull);
@@ -1780,7 +1805,7 @@ int find_batch(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, double now, co
     auto to_steps = [&]() { const int r2 = finish_deferred_copies(c); return r2 ? r2 : 2; };
     if (c->n_big_pods) return to_steps();                       // four-group pods: their set model is a kernel of its own
     if (cand && (rc = stage_cand(c, cand))) return rc;
-    if ((rc = ensure_records(c))) return rc;
+    if ((rc = ensure_records(c, P))) return rc;
     if (c->x_spill) return to_steps();
     constexpr uint32_t nw = 4;                                  // 256-thread blocks: a tile's pods are one wavefront of the mapping tail
     if ((rc = build_items(c, nw, true))) return rc;
@@ -1810,14 +1835,14 @@ int find_batch(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, double now, co
     FindNArgs a;
     memset(&a, 0, sizeof a);
     a.s.shapes_P = P;
-    fill_digest_args(c, p, 0, kWcPartsDefault, a.s.digest);     // (the digest is on the call's critical path here: the CPU rows cut four ways, as the one-tile find cuts them)
+    fill_digest_args(c, p, 0, kWcPartsDefault, P, a.s.digest);  // (the digest is on the call's critical path here: the CPU rows cut four ways, as the one-tile find cuts them)
     a.dig_parts = 1u + kWcPartsDefault;
     a.s.nb_digest = tiles * a.dig_parts;
     a.nb_lead = (a.s.nb_digest + 7u) & ~7u;
-    fill_fit_args(c, p, 0, now, a.s.fit, true);
+    fill_fit_args(c, p, 0, now, P, a.s.fit, true);
     a.s.fit.nm = nullptr; a.s.fit.dbg_skip = 0;                 // (no verdict matrix in this form)
     a.s.nb_fit = c->n_items;
-    a.s.finish_m = make_map_args(c, p, 0);
+    a.s.finish_m = make_map_args(c, p, 0, P);
     a.s.finish_m.out = h_maps;
     a.s.finish_h = make_shape_args(c, p, 0);
     a.want_map = map_out ? 1u : 0u; a.tiles = tiles;
@@ -1841,8 +1866,7 @@ int find_batch(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, double now, co
         a.tile_wcls = tail_d + items_bytes + counts_bytes;
     }
     a.sync = c->findn_sync.p; a.host_score = h_score; a.host_flag = h_flag; a.seq = seq;
-    size_t lds = lds_slice(c->lds_bytes) + (size_t)nw * 64 * sizeof(unsigned long long);
-    lds = std::max(lds, std::max(kDigestLds, map_tile_lds_bytes<256>()));
+    const size_t lds = std::max(fit_launch_lds(c, nw), std::max(kDigestLds, map_tile_lds_bytes<256>()));
     prof.lap("records, items, arguments");
     const auto t_launch = std::chrono::steady_clock::now();
     hipLaunchKernelGGL((k_findn<256>), dim3(a.nb_lead + a.s.nb_fit), dim3(256), lds, c->streams.use(0), a);
@@ -1850,11 +1874,9 @@ int find_batch(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, double now, co
     prof.lap("launch call");
     uint32_t seen = 0;
     TRY(poll_word(c, h_flag, seq, kFindAborted, t_launch, 2000, 0, seen));
-    if (seen != seq) {                                          // the launch gave up on a wait: counters back to zero, staged path
-        HIPCHK(c, c->streams.wait(0));
-        HIPCHK(c, hipMemsetAsync(c->findn_sync.p, 0, (size_t)c->findn_sync_words * sizeof(uint32_t), c->streams.use(0)));
-        *h_flag = 0;
-        c->n_items = 0;                                         // (the step's own work items: 512-thread blocks)
+    if (seen != seq) {                                          // the launch gave up on a wait: staged path
+        TRY(recover_abandoned_launch(c, c->findn_sync.p, c->findn_sync_words, h_flag));
+        c->n_items = 0;                                        // (the step's own work items: 512-thread blocks)
         return to_steps();
     }
     prof.lap("poll");
@@ -1863,7 +1885,7 @@ int find_batch(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, double now, co
     prof.lap("results to the caller's order");
     store_find_stats(c, (uint64_t)P * c->n, (uint64_t)tiles * c->n * 24ull + (uint64_t)P * sizeof(nhdfit_req) + (uint64_t)P * 8ull);
     c->stats.batch_finds++;
-    c->P = 0; c->n_items = 0;                                   // nothing stays staged for nhdfit_enqueue_step / nhdfit_fetch
+    end_staged_batch(c);                                        // nothing stays staged for nhdfit_enqueue_step / nhdfit_fetch
     c->streams.pipe0_drained_by_its_last_word();                // (the word came behind everything this call put on the stream)
     return NHDFIT_OK;
 }
@@ -1872,13 +1894,11 @@ int find_batch(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, double now, co
 int nhdfit_find(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, double now, const uint64_t* cand,
                 uint64_t* score_out, uint64_t* bitmap_out, nhdfit_mapping* map_out) {
     PhaseTimer prof{"find", P};
-    if (c && !bitmap_out) {
-        const int rs = find_small(c, reqs, P, now, cand, score_out, map_out);
-        if (rs <= 0) { prof.lap("single launch"); return rs; }
-    }
     int rc;
     bool staged = false;
     if (c && !bitmap_out) {
+        const int rs = find_small(c, reqs, P, now, cand, score_out, map_out);
+        if (rs <= 0) { prof.lap("single launch"); return rs; }
         const int rb = find_batch(c, reqs, P, now, cand, score_out, map_out);
         if (rb <= 0) { prof.lap("single launch, batch"); return rb; }
         staged = rb == 2;                                       // (the launch did not run: the staged batch takes the steps' path)
@@ -1896,13 +1916,6 @@ int nhdfit_find(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, double now, c
     prof.lap("fetch");
     return rc;
 }
-
-namespace {
-MapTables map_tables(nhdfit_ctx* c) {
-    return MapTables{c->asc.p, c->choose_tab.p, SetStates{c->st_info.p, c->st_next.p, c->st_asc.p, c->st_n}};
-}
-SigTable sig_table(nhdfit_ctx* c) { return SigTable{c->sig_keys.p, c->sig_ids.p, c->sig_mask}; }
-}  // namespace
 
 // ---- nodes beyond the fast layout (wide_core.h / wide_kernel.h) -------------------------------------------------------------
 int nhdfit_wide_count(nhdfit_ctx* c, uint32_t* n_wide) {
@@ -1988,14 +2001,7 @@ int nhdfit_wide_commit(nhdfit_ctx* c, uint32_t node, const nhdfit_req* req, cons
     if (slot < 0) return fail(c, NHDFIT_E_INVAL, "node %u is not a wide node", node);
     if (!map->valid) return fail(c, NHDFIT_E_INVAL, "the mapping is not valid");
     if (!req_valid(*req)) return fail(c, NHDFIT_E_INVAL, "the request is not valid (map type NUMA / PCI, 1..%d proc groups)", NHDFIT_MAX_GROUPS);
-    for (uint32_t g = 0; g <= req->n_groups; ++g) {
-        if (map->cpu[g] < 0 || map->cpu[g] >= NHDFIT_WIDE_MAX_NUMA) return fail(c, NHDFIT_E_INVAL, "mapping: cpu[%u] = %d is not a NUMA node", g, (int)map->cpu[g]);
-        if (g == req->n_groups) break;
-        if (map->gpu[g] < 0 || map->gpu[g] >= NHDFIT_WIDE_MAX_NUMA || map->nic_numa[g] < 0 || map->nic_numa[g] >= NHDFIT_WIDE_MAX_NUMA)
-            return fail(c, NHDFIT_E_INVAL, "mapping: group %u sits on NUMA node %d / its NIC on %d", g, (int)map->gpu[g], (int)map->nic_numa[g]);
-        if (map->nic_idx[g] < 0 || map->nic_idx[g] >= NHDFIT_MAX_NICS_PER_NUMA)
-            return fail(c, NHDFIT_E_INVAL, "mapping: group %u uses NIC ordinal %d", g, (int)map->nic_idx[g]);
-    }
+    TRY(check_mapping(c, map, req->n_groups, NHDFIT_WIDE_MAX_NUMA));
     HIPCHK(c, hipSetDevice(c->dev));
     TRY(sync_all(c));             // steps in flight read the wide records
     HIPCHK(c, c->wide_place.reserve(1));
@@ -2088,14 +2094,7 @@ int nhdfit_big_commit(nhdfit_ctx* c, uint32_t node, const nhdfit_big_req* req, c
     if (!req_valid(*req)) return fail(c, NHDFIT_E_INVAL, "the request is not valid (map type NUMA / PCI, 1..%d proc groups)", NHDFIT_BIG_MAX_GROUPS);
     const int slot = c->wide_slot(node);
     const int numa_lim = slot >= 0 ? NHDFIT_WIDE_MAX_NUMA : NHDFIT_MAX_NUMA;
-    for (uint32_t g = 0; g <= req->n_groups; ++g) {
-        if (map->cpu[g] < 0 || map->cpu[g] >= numa_lim) return fail(c, NHDFIT_E_INVAL, "mapping: cpu[%u] = %d is not a NUMA node", g, (int)map->cpu[g]);
-        if (g == req->n_groups) break;
-        if (map->gpu[g] < 0 || map->gpu[g] >= numa_lim || map->nic_numa[g] < 0 || map->nic_numa[g] >= numa_lim)
-            return fail(c, NHDFIT_E_INVAL, "mapping: group %u sits on NUMA node %d / its NIC on %d", g, (int)map->gpu[g], (int)map->nic_numa[g]);
-        if (map->nic_idx[g] < 0 || map->nic_idx[g] >= NHDFIT_MAX_NICS_PER_NUMA)
-            return fail(c, NHDFIT_E_INVAL, "mapping: group %u uses NIC ordinal %d", g, (int)map->nic_idx[g]);
-    }
+    TRY(check_mapping(c, map, req->n_groups, numa_lim));
     HIPCHK(c, hipSetDevice(c->dev));
     TRY(sync_all(c));             // the commit writes the mirror: steps in flight on either pipe read it
     HIPCHK(c, c->big_place.reserve(1));
@@ -2201,6 +2200,232 @@ int schedule_batch_general(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, do
     *n_done = done;
     return NHDFIT_OK;
 }
+// ---- mode B on ordinary nodes: a snapshot pass, then the batch decided pod by pod on the device (seq_kernel.h, seq2_kernel.h) -----
+// Snapshot pass - digest + fit on pipe 0: the verdict matrix and the first-fit scores - and what the sequential kernels read beside it.
+int seq_snapshot(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, double now, const uint64_t* cand) {
+    {
+        // the verdict matrix, no mapping roles (every placement of the batch is mapped against the node's state at ITS turn), and
+        // every signature's rows: the decisions read R rows for states no node is in yet (a committed node's new signature)
+        Scoped<bool> bitmap(c->want_bitmap, true), map(c->want_map, false), sigs(c->all_sigs, true);
+        TRY(nhdfit_stage_requests(c, reqs, P));
+        if (cand) TRY(stage_cand(c, cand));
+        TRY(nhdfit_enqueue_step(c, now));
+    }
+    Pipe& p = c->pipe[0];                                       // (the one step a freshly staged batch enqueues runs on pipe 0)
+    SeqBufs& q = c->seq;
+    const uint32_t chunks = (c->n + 63) / 64, tiles = (P + kTile - 1) / kTile;
+    HIPCHK(c, q.reserve(P, c->n, chunks, tiles));
+    // caller's pod -> staged (class-sorted) position, and behind it the decision engine's list [the pods without GPUs | every other
+    // pod] (caller's indices ascending): one page-locked block, ONE copy command (each costs the copy engine ~10 us; out of pageable
+    // memory the runtime stages it besides)
+    uint32_t* order_h = q.pin_order.p;
+    uint32_t* tn_h = q.pin_order.p + P;
+    for (uint32_t i = 0; i < P; ++i) order_h[c->perm[i]] = i;
+    uint32_t at = 0;
+    q.tn_n = 0;
+    for (int pass = 0; pass < 2; ++pass) {
+        for (uint32_t i = 0; i < P; ++i) {
+            uint32_t g = 0;
+            const bool valid = req_valid(reqs[i]);
+            if (valid) for (uint32_t k = 0; k < reqs[i].n_groups; ++k) g += reqs[i].gpus[k];
+            if ((valid && g == 0) == (pass == 0)) tn_h[at++] = i;
+        }
+        if (pass == 0) q.tn_n = at;
+    }
+    HIPCHK(c, hipMemcpyAsync(q.order.p, order_h, 2 * (size_t)P * sizeof(uint32_t), hipMemcpyHostToDevice, c->streams.use(0)));
+    hipLaunchKernelGGL(k_nogpu, dim3(chunks), dim3(64), 0, c->streams.use(0), c->p2.p, c->n, q.nogpu.p);
+    const int b0 = (int)((p.n_fit - 1) % kBufs);
+    hipLaunchKernelGGL(k_tile_masks, dim3(tiles), dim3(64), 0, c->streams.use(0), p.hdr[b0].p, tiles, q.tile_masks.p);
+    HIPCHK(c, hipGetLastError());
+    return NHDFIT_OK;
+}
+// What the sequential kernels of either form work on: the mirror, the snapshot's results, the batch's own state.
+SeqArgs make_seq_args(nhdfit_ctx* c, uint32_t P, double now) {
+    Pipe& p = c->pipe[0];
+    SeqBufs& q = c->seq;
+    const int b = (int)((p.n_fit - 1) % kBufs);
+    SeqArgs sa;
+    memset(&sa, 0, sizeof sa);
+    sa.p0 = c->p0.p; sa.p1 = c->p1.p; sa.p2 = c->p2.p; sa.p3 = c->p3.p; sa.p4 = c->p4.p; sa.det = c->det.p;
+    sa.n = c->n; sa.chunks = (c->n + 63) / 64; sa.global_base = c->global_base; sa.now = now;
+    sa.reqs = c->reqs.p; sa.score = p.score[b].p; sa.P = P; sa.order = q.order.p;
+    sa.tabs = p.tabs[b].p; sa.pitch = c->pitch; sa.tile_wcls = c->tile_wcls.p;
+    for (int w = 0; w < kWClasses; ++w) sa.L[w] = c->L[w];
+    sa.rows = q.rows_t.p; sa.taken = q.taken.p; sa.nogpu = q.nogpu.p; sa.tile_masks = q.tile_masks.p;
+    sa.caps = c->caps.p; sa.sigs = sig_table(c); sa.fc_dim = c->max_cores + 1; sa.fg_dim = c->max_gpus + 1; sa.ngs = c->ngs;
+    sa.mt = map_tables(c);
+    sa.undo = q.undo.p; sa.touched = q.touched.p; sa.counters = q.seq_counters.p; sa.keep_undo = 1;
+    sa.out = q.seq_out.p; sa.place = q.seq_place.p; sa.n_done = q.seq_counters.p + 1; sa.gl_tiles = q.gl_tiles.p;
+    return sa;
+}
+// Pod-major verdict rows of the snapshot + empty taken / first-touch state (again before a fallback pass).  One launch clears
+// everything a pass starts from - seven fill commands in a row cost more than the fills; queue_len != 0 adds the decision engine's words.
+int reset_scan_state(nhdfit_ctx* c, uint32_t queue_len) {
+    SeqBufs& q = c->seq;
+    const uint32_t chunks = (c->n + 63) / 64, tiles = (c->P + kTile - 1) / kTile, groups = (chunks + kRowsTChunks - 1) / kRowsTChunks;
+    // (the sequential kernels' copy of the verdict matrix, [P][chunks]; stream order is all they need)
+    hipLaunchKernelGGL(k_rows_t, dim3((tiles * groups + 3) / 4), dim3(256), 0, c->streams.use(0), c->pipe[0].nm.p, q.rows_t.p, chunks, c->P);
+    HIPCHK(c, hipGetLastError());
+    SeqResetArgs ra;
+    memset(&ra, 0, sizeof ra);
+    ra.taken = q.taken.p; ra.chunks = chunks ? chunks : 1; ra.touched = q.touched.p; ra.n = c->n;
+    ra.counters = q.seq_counters.p; ra.flags = q.seq_flags.p;
+    if (queue_len) { ra.ctrl = q.seq_ctrl.p; ra.mat = q.seq_mat.p; ra.queue = q.seq_queue.p; ra.queue_len = queue_len; }
+    const uint32_t most = std::max(std::max(ra.chunks, ra.n), ra.queue_len);
+    hipLaunchKernelGGL(k_seq_reset, dim3(std::min<uint32_t>((most + 255) / 256, 1024u)), dim3(256), 0, c->streams.use(0), ra);
+    HIPCHK(c, hipGetLastError());
+    return NHDFIT_OK;
+}
+// Tuning aid (NHDFIT_SEQ_PROF): what the general kernel / the decision engine left in its clock words.
+int report_seq_prof(nhdfit_ctx* c) {
+    unsigned long long t[16];
+    HIPCHK(c, c->streams.wait(0));
+    HIPCHK(c, hipMemcpy(t, c->role_clock.p, sizeof t, hipMemcpyDeviceToHost));
+    const double per = 0.01 / (double)(t[3] ? t[3] : 1);
+    fprintf(stderr, "[nhdfit] k_seq wave 0 per round: node load %.1f, NIC bits %.1f, mapping %.1f, commit %.1f, write-back %.1f us\n",
+            t[5] * per, t[6] * per, t[7] * per, t[8] * per, t[9] * per);
+    fprintf(stderr, "[nhdfit] k_seq: %llu pods in %llu rounds; scan %.1f us, pick %.1f us, map+commit %.1f us, columns %.1f us per round\n", t[4], t[3],
+            t[0] * per, t[2] * per, t[1] * per, t[10] * per);
+    fprintf(stderr, "[nhdfit] k_seq columns: evaluate %.1f, patch %.1f, fence %.1f, barrier %.1f us per round; %.1f (node, tile) pairs per round\n",
+            t[11] * per, t[12] * per, t[13] * per, t[14] * per, (double)t[15] / (double)(t[3] ? t[3] : 1));
+    return NHDFIT_OK;
+}
+int report_decide_prof(nhdfit_ctx* c) {
+    uint32_t ctl[32];
+    HIPCHK(c, hipMemcpy(ctl, c->seq.seq_ctrl.p, sizeof ctl, hipMemcpyDeviceToHost));
+    fprintf(stderr, "[nhdfit] k_decide: %u queue items; GPU-less pods: %u verifications failed, %u looked at a node in LDS, %u at a published one, "
+                    "%u at an untouched one, %u waited for an earlier pod's target, %u window rescans, %u sent back by the sequencer\n",
+            ctl[1] ? ctl[1] - 1 : 0, ctl[4], ctl[5], ctl[6], ctl[7], ctl[8], ctl[14], ctl[15]);
+    fprintf(stderr, "[nhdfit] k_decide sequencer: waiting for fetchers %.2f ms, pods with GPUs %.2f ms, GPU-less pods: waiting for their speculators %.2f ms, "
+                    "validation %.2f ms\n", ctl[9] * 1e-5, ctl[10] * 1e-5, ctl[11] * 1e-5, ctl[12] * 1e-5);
+    fprintf(stderr, "[nhdfit] k_decide fetcher 0: waiting for list entries / windows %.2f ms, for the ring %.2f ms, issue + park %.2f ms\n", ctl[2] * 1e-5, ctl[3] * 1e-5, ctl[13] * 1e-5);
+    fprintf(stderr, "[nhdfit] k_decide sequencer, a pod with GPUs: window + pick %.2f ms, take %.2f ms, queue entry %.2f ms\n", ctl[28] * 1e-5, ctl[29] * 1e-5, ctl[30] * 1e-5);
+    fprintf(stderr, "[nhdfit] k_decide speculators, finer: candidate pick %.2f ms, pre-checks %.2f ms, NIC bits %.2f ms, (mapping = verification), before post %.2f ms, "
+                    "post + first-touch + result %.2f ms, (summary = stage 1)\n", ctl[23] * 1e-5, ctl[24] * 1e-5, ctl[25] * 1e-5, ctl[26] * 1e-5, ctl[27] * 1e-5);
+    fprintf(stderr, "[nhdfit] k_decide speculators (%d, summed): set-up %.2f ms, node state %.2f ms, verification %.2f ms, commit stage 1 %.2f ms, waiting (sequencer, earlier pods) %.2f ms, "
+                    "commit stage 2 %.2f ms, publication %.2f ms\n", kSpecWaves, ctl[16] * 1e-5, ctl[17] * 1e-5, ctl[18] * 1e-5, ctl[19] * 1e-5, ctl[20] * 1e-5, ctl[22] * 1e-5, ctl[21] * 1e-5);
+    return NHDFIT_OK;
+}
+// The general kernel: one block walks the batch's pods in order, kSeqPods per round; pods [0, done) of the caller's order get decided.
+int run_general_kernel(nhdfit_ctx* c, const SeqArgs& sa, uint32_t& done) {
+    const uint32_t P = sa.P, tiles = (P + kTile - 1) / kTile;
+    SeqArgs g = sa;
+    g.list = nullptr; g.n_list = 0;                             // (all P pods)
+    size_t seq_lds = lds_slice((size_t)tiles * 16) + lds_slice(((size_t)c->sig_mask + 1) * 8) + lds_slice(((size_t)c->sig_mask + 1) * 4) + lds_slice((size_t)P * 4) + lds_slice(tiles);
+    g.lds_tables = seq_lds <= 96 * 1024;
+    if (!g.lds_tables) seq_lds = 0;
+    HIPCHK(c, hipFuncSetAttribute((const void*)k_seq<16>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));   // sixteen pods per round
+    const bool seq_prof = tune_env("NHDFIT_SEQ_PROF") != nullptr;
+    if (seq_prof) { HIPCHK(c, c->role_clock.reserve(16)); g.prof = c->role_clock.p; }
+    hipLaunchKernelGGL(k_seq<16>, dim3(1), dim3(1024), seq_lds, c->streams.use(0), g);
+    HIPCHK(c, hipGetLastError());
+    if (seq_prof) TRY(report_seq_prof(c));
+    uint32_t counters[4] = {0, 0, 0, 0};
+    HIPCHK(c, hipMemcpyAsync(counters, c->seq.seq_counters.p, sizeof counters, hipMemcpyDeviceToHost, c->streams.use(0)));
+    HIPCHK(c, c->streams.wait(0));
+    done = counters[1];
+    return NHDFIT_OK;
+}
+// Every node the batch touched goes back to its first-touch copy.
+int undo_batch(nhdfit_ctx* c, const SeqArgs& sa) {
+    hipLaunchKernelGGL(k_undo, dim3(sa.P), dim3(64), 0, c->streams.use(0), sa);
+    HIPCHK(c, hipGetLastError());
+    return NHDFIT_OK;
+}
+
+// The decision engine (seq2_kernel.h) takes every batch its block 0 has the LDS for: two bit maps over the nodes, one entry per
+// GPU-less pod (the multiset of their commits), one bit per pod; the optional tables - signature hash, set states, choose table, in
+// that order - go in after those.  The two node bit maps may stop short of the mirror (DecideArgs::span: config 5's whole cluster is
+// 4 096 chunks, 64 KB on their own); they then cover what the 64 KB leave, at least 512 chunks, and a decision past them sends the
+// batch to the general kernel.  What the block may ask for is the CU's 160 KB less the kernel's own static LDS (read from the code
+// object: it moves with every edit of seq2_kernel.h - the optional tables were once admitted against fixed marks that assumed 45 KB of
+// it and a batch whose tables all fitted those marks was refused by hipFuncSetAttribute, found by tools/soak_mode_b_gpu.py).
+struct DecideLds { uint32_t hash_slots, span, queue_len; size_t dyn; bool sigs, states, choose, ok; };
+DecideLds decide_lds(uint32_t chunks, uint32_t P, uint32_t n_gpu_less, uint32_t sig_mask, uint32_t st_n, size_t static_lds, uint32_t force_span) {
+    DecideLds a{};
+    a.hash_slots = decide_hash_slots(n_gpu_less);
+    const size_t dyn_fixed = lds_slice((size_t)a.hash_slots * 4) + lds_slice((size_t)((P + 31) / 32) * 4);
+    a.span = chunks;
+    if (2 * lds_slice((size_t)chunks * 8) + dyn_fixed > 64 * 1024)
+        a.span = dyn_fixed + 2 * 512 * 8 <= 64 * 1024 ? (uint32_t)((64 * 1024 - dyn_fixed) / 16) & ~15u : 0u;
+    if (force_span && force_span < a.span) a.span = force_span;
+    a.dyn = 2 * lds_slice((size_t)a.span * 8) + dyn_fixed;
+    const size_t dyn_room = static_lds < 160 * 1024 ? 160 * 1024 - static_lds : 0;
+    a.ok = a.span > 0 && P < (1u << 26) && a.dyn <= dyn_room;
+    a.queue_len = a.ok ? P * 4u : 0u;                           // a commit per pod + up to three patch items per commit of a GPU-less pod
+    const size_t sig_bytes = lds_slice(((size_t)sig_mask + 1) * 8) + lds_slice(((size_t)sig_mask + 1) * 4);
+    const size_t st_bytes = lds_slice((size_t)st_n * 8) + lds_slice((size_t)st_n * 32) + lds_slice(256 * 4);
+    const size_t room96 = dyn_room < 96 * 1024 ? dyn_room : 96 * 1024, room112 = dyn_room < 112 * 1024 ? dyn_room : 112 * 1024;
+    if (a.dyn + sig_bytes <= room96) { a.sigs = true; a.dyn += sig_bytes; }
+    if (st_n && a.dyn + st_bytes <= room96) { a.states = true; a.dyn += st_bytes; }
+    if (a.dyn + lds_slice(kChooseEntries) <= room112) { a.choose = true; a.dyn += lds_slice(kChooseEntries); }
+    return a;
+}
+// ... for this batch on this context: `any_g4` picks the instantiation (four-group pods: the one that carries the generic set model).
+int admit_decision_engine(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, bool& any_g4, DecideLds& lds) {
+    any_g4 = false;
+    for (uint32_t i = 0; i < P && !any_g4; ++i) any_g4 = reqs[i].n_groups > 3;
+    static size_t decide_static[2] = {0, 0};
+    if (!decide_static[any_g4]) {
+        hipFuncAttributes fa;
+        HIPCHK(c, hipFuncGetAttributes(&fa, any_g4 ? (const void*)k_decide<true> : (const void*)k_decide<false>));
+        decide_static[any_g4] = fa.sharedSizeBytes ? fa.sharedSizeBytes : 1;
+    }
+    static const uint32_t force_span = tune_env("NHDFIT_SEQ_SPAN") ? (uint32_t)atoi(tune_env("NHDFIT_SEQ_SPAN")) : 0u;   // tuning aid (tests of the fallback)
+    lds = decide_lds((c->n + 63) / 64, P, c->seq.tn_n, c->sig_mask, c->st_n, decide_static[any_g4], force_span);
+    lds.ok = lds.ok && !c->seq_general && c->n > 0;
+    return NHDFIT_OK;
+}
+// One block decides, the rest of the grid commits.  `gave_back`: a NIC state without a signature id (or a wait that ran out) - the
+// caller starts over with the kernel whose stop / intern / resume protocol the caller of nhdfit_schedule_batch knows.
+int run_decision_engine(nhdfit_ctx* c, const SeqArgs& sa, const DecideLds& lds, bool any_g4, bool& gave_back) {
+    SeqBufs& q = c->seq;
+    const uint32_t P = sa.P, n_n = q.tn_n, n_g = P - q.tn_n;
+    const uint32_t* list_dev = q.order.p + P;                   // [the pods without GPUs | every other pod] (uploaded behind the order)
+    hipLaunchKernelGGL(k_decide_prep, dim3((P + 255) / 256), dim3(256), 0, c->streams.use(0), list_dev, P, q.order.p, sa.score, c->global_base, q.seq_ent.p);
+    HIPCHK(c, hipGetLastError());
+    DecideArgs qa;
+    memset(&qa, 0, sizeof qa);
+    qa.list_n = list_dev; qa.n_n = n_n; qa.list_g = list_dev + n_n; qa.n_g = n_g; qa.ent_n = q.seq_ent.p; qa.ent_g = q.seq_ent.p + n_n; qa.queue_len = lds.queue_len; qa.ncls = c->ncls;
+    qa.hash_slots = lds.hash_slots;
+    qa.span = lds.span;
+    qa.dbg = tune_env("NHDFIT_SEQ_SKIP") ? (uint32_t)atoi(tune_env("NHDFIT_SEQ_SKIP")) : 0u;
+    qa.s = sa; qa.queue = q.seq_queue.p; qa.ctrl = q.seq_ctrl.p; qa.mat = q.seq_mat.p; qa.flags = q.seq_flags.p;
+    qa.lds_sigs = lds.sigs; qa.lds_states = lds.states; qa.lds_choose = lds.choose;
+    HIPCHK(c, hipFuncSetAttribute(any_g4 ? (const void*)k_decide<true> : (const void*)k_decide<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds.dyn));
+    if (any_g4) hipLaunchKernelGGL(k_decide<true>, dim3(1 + kWorkerBlocks), dim3(64 * kDecideWaves), lds.dyn, c->streams.use(0), qa);
+    else hipLaunchKernelGGL(k_decide<false>, dim3(1 + kWorkerBlocks), dim3(64 * kDecideWaves), lds.dyn, c->streams.use(0), qa);
+    HIPCHK(c, hipGetLastError());
+    uint32_t flags[4] = {0, 0, 0, 0};
+    HIPCHK(c, hipMemcpyAsync(flags, q.seq_flags.p, sizeof flags, hipMemcpyDeviceToHost, c->streams.use(0)));
+    HIPCHK(c, c->streams.wait(0));
+    if (tune_env("NHDFIT_SEQ_PROF")) TRY(report_decide_prof(c));
+    gave_back = flags[1] || flags[3];
+    return NHDFIT_OK;
+}
+// The batch's results to the caller, in the caller's order; the records of the nodes it committed to are stale.
+int collect_seq_results(nhdfit_ctx* c, uint32_t P, uint32_t decided, int apply, int64_t* node_out, nhdfit_mapping* map_out,
+                        nhdfit_placement* place_out, int32_t* status_out) {
+    SeqBufs& q = c->seq;
+    q.seq_host.resize(P);
+    HIPCHK(c, hipMemcpyAsync(q.seq_host.data(), q.seq_out.p, P * sizeof(SeqResult), hipMemcpyDeviceToHost, c->streams.use(0)));
+    if (place_out) HIPCHK(c, hipMemcpyAsync(place_out, q.seq_place.p, (size_t)P * sizeof(nhdfit_placement), hipMemcpyDeviceToHost, c->streams.use(0)));
+    TRY(nhdfit_sync(c));
+    int64_t lo = -1, hi = -1;
+    for (uint32_t i = 0; i < decided; ++i) {
+        const SeqResult& o = q.seq_host[i];
+        node_out[i] = o.node;
+        if (map_out) map_out[i] = o.map;
+        if (status_out) status_out[i] = o.status;
+        if (o.node >= 0) {
+            const int64_t v = o.node - (int64_t)c->global_base;
+            lo = lo < 0 || v < lo ? v : lo;
+            hi = v + 1 > hi ? v + 1 : hi;
+        }
+    }
+    if (apply && lo >= 0) mark_records_stale(c, (uint32_t)lo, (uint32_t)hi);
+    return NHDFIT_OK;
+}
 }  // namespace
 
 int nhdfit_schedule_batch(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, double now, const uint64_t* cand, int apply,
@@ -2212,247 +2437,35 @@ int nhdfit_schedule_batch(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, dou
     // mode B across shards (nhd_amd/sharding.py hands the pods a shard could not place to the next rank), so its snapshot step
     // must not all-reduce its scores with ranks that are working on other slices.  (Round 4 refused the call outright; the ring's
     // first run on real ranks would have ended there - found by the rank-to-rank GPU test of round 5.)
-    struct CommOff {
-        nhdfit_ctx* c; ncclComm_t saved;
-        explicit CommOff(nhdfit_ctx* c_) : c(c_), saved(c_->comm) { c->comm = nullptr; }
-        ~CommOff() { c->comm = saved; }
-    };
     if (c->comm) TRY(sync_all(c));   // (steps of a staged batch still carry their all-reduce)
-    CommOff comm_off(c);
+    Scoped<ncclComm_t> comm_off(c->comm, nullptr);
     if (!std::isfinite(now)) return fail(c, NHDFIT_E_INVAL, "now must be finite (a placed node is busy at `now`)");
     HIPCHK(c, hipSetDevice(c->dev));
     c->wide_places_last.clear();
+    // wide nodes: no decision engine, the scheduler's loop pod by pod
     if (c->n_wide) return schedule_batch_general(c, reqs, P, now, cand, apply, node_out, map_out, place_out, status_out, n_done);
-    Pipe& p = c->pipe[0];                                       // (the one step a freshly staged batch enqueues runs on pipe 0)
-    const uint32_t chunks = (c->n + 63) / 64;
-    const uint32_t tiles = (P + kTile - 1) / kTile;
-    int rc;
-    {
-        // snapshot pass: digest + fit (verdict matrix and first-fit scores; the mapping roles are not needed - every
-        // placement of the batch is mapped against the node's state at ITS turn)
-        const bool wb = c->want_bitmap, wm = c->want_map;
-        c->want_bitmap = true; c->want_map = false;
-        c->all_sigs = true;                              // the decisions read R rows for states no node is in yet (a committed node's new signature)
-        rc = nhdfit_stage_requests(c, reqs, P);
-        if (!rc && cand) rc = stage_cand(c, cand);
-        if (!rc) rc = nhdfit_enqueue_step(c, now);
-        c->all_sigs = false;
-        c->want_bitmap = wb; c->want_map = wm;
-        if (rc) return rc;
-        HIPCHK(c, c->nogpu.reserve(chunks ? chunks : 1));
-        HIPCHK(c, c->taken.reserve(chunks ? chunks : 1));
-        HIPCHK(c, c->tile_masks.reserve((size_t)tiles * 2));
-        HIPCHK(c, c->touched.reserve(c->n ? c->n : 1));
-        HIPCHK(c, c->gl_tiles.reserve(tiles));
-        HIPCHK(c, c->seq_counters.reserve(4));
-        HIPCHK(c, c->undo.reserve(P));
-        HIPCHK(c, c->seq_out.reserve(P));
-        HIPCHK(c, c->seq_place.reserve(P));
-        HIPCHK(c, c->seq_ctrl.reserve(32));
-        HIPCHK(c, c->seq_ent.reserve(P));
-        HIPCHK(c, c->seq_mat.reserve(c->n ? c->n : 1));
-        HIPCHK(c, c->seq_flags.reserve(4));
-        HIPCHK(c, c->rows_t.reserve((size_t)chunks * P));         // (convert_rows_t's: the arguments below hold its address before the first pass fills it)
-        // caller's pod -> staged (class-sorted) position, and behind it the decision engine's list [the pods without GPUs | every other
-        // pod] (caller's indices ascending): one page-locked block, ONE copy command (each costs the copy engine ~10 us; out of pageable
-        // memory the runtime stages it besides)
-        HIPCHK(c, c->order.reserve(2 * (size_t)P));
-        HIPCHK(c, c->pin_order.reserve(2 * (size_t)P));
-        uint32_t* order_h = c->pin_order.p;
-        uint32_t* tn_h = c->pin_order.p + P;
-        for (uint32_t i = 0; i < P; ++i) order_h[c->perm[i]] = i;
-        {
-            uint32_t at = 0;
-            c->tn_n = 0;
-            for (int pass = 0; pass < 2; ++pass) {
-                for (uint32_t i = 0; i < P; ++i) {
-                    uint32_t g = 0;
-                    const bool valid = req_valid(reqs[i]);
-                    if (valid) for (uint32_t k = 0; k < reqs[i].n_groups; ++k) g += reqs[i].gpus[k];
-                    if ((valid && g == 0) == (pass == 0)) tn_h[at++] = i;
-                }
-                if (pass == 0) c->tn_n = at;
-            }
-        }
-        HIPCHK(c, hipMemcpyAsync(c->order.p, order_h, 2 * (size_t)P * sizeof(uint32_t), hipMemcpyHostToDevice, c->streams.use(0)));
-        hipLaunchKernelGGL(k_nogpu, dim3(chunks), dim3(64), 0, c->streams.use(0), c->p2.p, c->n, c->nogpu.p);
-        const int b0 = (int)((p.n_fit - 1) % kBufs);
-        hipLaunchKernelGGL(k_tile_masks, dim3(tiles), dim3(64), 0, c->streams.use(0), p.hdr[b0].p, tiles, c->tile_masks.p);
-        HIPCHK(c, hipGetLastError());
-    }
-    // pod-major verdict rows of the snapshot + empty taken / first-touch state (again before a fallback pass)
-    // (one launch clears everything a pass starts from - seven fill commands in a row cost more than the fills: `engine` adds the
-    // decision engine's words)
-    uint32_t queue_len = 0;
-    auto reset_scan_state = [&](bool engine) -> int {
-        TRY(convert_rows_t(c, p));
-        SeqResetArgs ra;
-        memset(&ra, 0, sizeof ra);
-        ra.taken = c->taken.p; ra.chunks = chunks ? chunks : 1; ra.touched = c->touched.p; ra.n = c->n;
-        ra.counters = c->seq_counters.p; ra.flags = c->seq_flags.p;
-        if (engine) { ra.ctrl = c->seq_ctrl.p; ra.mat = c->seq_mat.p; ra.queue = c->seq_queue.p; ra.queue_len = queue_len; }
-        const uint32_t most = std::max(std::max(ra.chunks, ra.n), ra.queue_len);
-        hipLaunchKernelGGL(k_seq_reset, dim3(std::min<uint32_t>((most + 255) / 256, 1024u)), dim3(256), 0, c->streams.use(0), ra);
-        HIPCHK(c, hipGetLastError());
-        return NHDFIT_OK;
-    };
-    const int b = (int)((p.n_fit - 1) % kBufs);
-    SeqArgs sa;
-    memset(&sa, 0, sizeof sa);
-    sa.p0 = c->p0.p; sa.p1 = c->p1.p; sa.p2 = c->p2.p; sa.p3 = c->p3.p; sa.p4 = c->p4.p; sa.det = c->det.p;
-    sa.n = c->n; sa.chunks = chunks; sa.global_base = c->global_base; sa.now = now;
-    sa.reqs = c->reqs.p; sa.score = p.score[b].p; sa.P = P; sa.order = c->order.p;
-    sa.tabs = p.tabs[b].p; sa.pitch = c->pitch; sa.tile_wcls = c->tile_wcls.p;
-    for (int w = 0; w < kWClasses; ++w) sa.L[w] = c->L[w];
-    sa.rows = c->rows_t.p; sa.taken = c->taken.p; sa.nogpu = c->nogpu.p; sa.tile_masks = c->tile_masks.p;
-    sa.caps = c->caps.p; sa.sigs = sig_table(c); sa.fc_dim = c->max_cores + 1; sa.fg_dim = c->max_gpus + 1; sa.ngs = c->ngs;
-    sa.mt = map_tables(c);
-    sa.undo = c->undo.p; sa.touched = c->touched.p; sa.counters = c->seq_counters.p; sa.keep_undo = 1;
-    sa.out = c->seq_out.p; sa.place = c->seq_place.p; sa.n_done = c->seq_counters.p + 1; sa.gl_tiles = c->gl_tiles.p;
-
-    // The general kernel: one block walks `n_list` pods (all P when list is null) in order, kSeqPods per round.
-    auto run_general = [&](const uint32_t* list_dev, uint32_t n_list, uint32_t& done) -> int {
-        SeqArgs g = sa;
-        g.list = list_dev; g.n_list = n_list;
-        size_t seq_lds = lds_slice((size_t)tiles * 16) + lds_slice(((size_t)c->sig_mask + 1) * 8) + lds_slice(((size_t)c->sig_mask + 1) * 4) + lds_slice((size_t)P * 4) + lds_slice(tiles);
-        g.lds_tables = seq_lds <= 96 * 1024;
-        if (!g.lds_tables) seq_lds = 0;
-        HIPCHK(c, hipFuncSetAttribute((const void*)k_seq<16>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));   // sixteen pods per round
-        const bool seq_prof = tune_env("NHDFIT_SEQ_PROF") != nullptr;
-        if (seq_prof) { HIPCHK(c, c->role_clock.reserve(16)); g.prof = c->role_clock.p; }
-        hipLaunchKernelGGL(k_seq<16>, dim3(1), dim3(1024), seq_lds, c->streams.use(0), g);
-        HIPCHK(c, hipGetLastError());
-        if (seq_prof) {
-            unsigned long long t[16];
-            HIPCHK(c, c->streams.wait(0));
-            HIPCHK(c, hipMemcpy(t, c->role_clock.p, sizeof t, hipMemcpyDeviceToHost));
-            const double per = 0.01 / (double)(t[3] ? t[3] : 1);
-            fprintf(stderr, "[nhdfit] k_seq wave 0 per round: node load %.1f, NIC bits %.1f, mapping %.1f, commit %.1f, write-back %.1f us\n",
-                    t[5] * per, t[6] * per, t[7] * per, t[8] * per, t[9] * per);
-            fprintf(stderr, "[nhdfit] k_seq: %llu pods in %llu rounds; scan %.1f us, pick %.1f us, map+commit %.1f us, columns %.1f us per round\n", t[4], t[3],
-                    t[0] * per, t[2] * per, t[1] * per, t[10] * per);
-            fprintf(stderr, "[nhdfit] k_seq columns: evaluate %.1f, patch %.1f, fence %.1f, barrier %.1f us per round; %.1f (node, tile) pairs per round\n",
-                    t[11] * per, t[12] * per, t[13] * per, t[14] * per, (double)t[15] / (double)(t[3] ? t[3] : 1));
-        }
-        uint32_t counters[4] = {0, 0, 0, 0};
-        HIPCHK(c, hipMemcpyAsync(counters, c->seq_counters.p, sizeof counters, hipMemcpyDeviceToHost, c->streams.use(0)));
-        HIPCHK(c, c->streams.wait(0));
-        done = counters[1];
-        return NHDFIT_OK;
-    };
-    auto undo_all = [&]() -> int {                              // every node this batch touched goes back to its first-touch copy
-        hipLaunchKernelGGL(k_undo, dim3(P), dim3(64), 0, c->streams.use(0), sa);
-        HIPCHK(c, hipGetLastError());
-        return NHDFIT_OK;
-    };
-
+    TRY(seq_snapshot(c, reqs, P, now, cand));
+    const SeqArgs sa = make_seq_args(c, P, now);
+    bool any_g4 = false;
+    DecideLds lds;
+    TRY(admit_decision_engine(c, reqs, P, any_g4, lds));
+    bool engine = lds.ok;
+    if (engine) HIPCHK(c, c->seq.seq_queue.reserve(lds.queue_len));
+    TRY(reset_scan_state(c, engine ? lds.queue_len : 0u));
     uint32_t decided = 0;                                       // pods [0, decided) of the caller's order are decided
-    // The decision engine (seq2_kernel.h) takes every batch its block 0 has the LDS for: two bit maps over the nodes, one entry per
-    // GPU-less pod (the multiset of their commits), one bit per pod; the optional tables go in after those.
-    const uint32_t n_gpu_less = c->tn_n;
-    const uint32_t hash_slots = decide_hash_slots(n_gpu_less);
-    // (the two node bit maps may stop short of the mirror - DecideArgs::span: config 5's whole cluster is 4 096 chunks, 64 KB on their own;
-    // they then cover what the 64 KB leave, at least 512 chunks, and a decision past them sends the batch to the general kernel)
-    const size_t dyn_fixed = lds_slice((size_t)hash_slots * 4) + lds_slice((size_t)((P + 31) / 32) * 4);
-    uint32_t span = chunks;
-    if (2 * lds_slice((size_t)chunks * 8) + dyn_fixed > 64 * 1024)
-        span = dyn_fixed + 2 * 512 * 8 <= 64 * 1024 ? (uint32_t)((64 * 1024 - dyn_fixed) / 16) & ~15u : 0u;
-    static const uint32_t force_span = tune_env("NHDFIT_SEQ_SPAN") ? (uint32_t)atoi(tune_env("NHDFIT_SEQ_SPAN")) : 0u;   // tuning aid (tests of the fallback)
-    if (force_span && force_span < span) span = force_span;
-    const size_t dyn_base = 2 * lds_slice((size_t)span * 8) + dyn_fixed;
-    bool any_g4 = false;                                        // (four-group pods: the instantiation that carries the generic set model)
-    for (uint32_t i = 0; i < P && !any_g4; ++i) any_g4 = reqs[i].n_groups > 3;
-    // What the block may ask for is the CU's 160 KB less the kernel's own static LDS (read from the code object: it moves with every edit
-    // of seq2_kernel.h - the optional tables were once admitted against fixed marks that assumed 45 KB of it and a batch whose tables all
-    // fitted those marks was refused by hipFuncSetAttribute, found by tools/soak_mode_b_gpu.py).
-    static size_t decide_static[2] = {0, 0};
-    if (!decide_static[any_g4]) {
-        hipFuncAttributes fa;
-        HIPCHK(c, hipFuncGetAttributes(&fa, any_g4 ? (const void*)k_decide<true> : (const void*)k_decide<false>));
-        decide_static[any_g4] = fa.sharedSizeBytes ? fa.sharedSizeBytes : 1;
-    }
-    const size_t dyn_room = decide_static[any_g4] < 160 * 1024 ? 160 * 1024 - decide_static[any_g4] : 0;
-    bool fast = !c->seq_general && span > 0 && c->n > 0 && P < (1u << 26) && dyn_base <= dyn_room;
-    if (fast) {
-        queue_len = P * 4u;                                     // a commit per pod + up to three patch items per commit of a GPU-less pod
-        HIPCHK(c, c->seq_queue.reserve(queue_len));
-    }
-    if ((rc = reset_scan_state(fast))) return rc;
-    if (fast) {
-        // The decision engine (seq2_kernel.h): one block decides, the rest of the grid commits.
-        const uint32_t* list_dev = c->order.p + P;              // [the pods without GPUs | every other pod] (uploaded behind the order)
-        const uint32_t n_n = c->tn_n, n_g = P - c->tn_n;
-        hipLaunchKernelGGL(k_decide_prep, dim3((P + 255) / 256), dim3(256), 0, c->streams.use(0), list_dev, P, c->order.p, p.score[b].p, c->global_base, c->seq_ent.p);
-        HIPCHK(c, hipGetLastError());
-        DecideArgs qa;
-        memset(&qa, 0, sizeof qa);
-        qa.list_n = list_dev; qa.n_n = n_n; qa.list_g = list_dev + n_n; qa.n_g = n_g; qa.ent_n = c->seq_ent.p; qa.ent_g = c->seq_ent.p + n_n; qa.queue_len = queue_len; qa.ncls = c->ncls;
-        qa.hash_slots = hash_slots;
-        qa.span = span;
-        qa.dbg = tune_env("NHDFIT_SEQ_SKIP") ? (uint32_t)atoi(tune_env("NHDFIT_SEQ_SKIP")) : 0u;
-        qa.s = sa; qa.queue = c->seq_queue.p; qa.ctrl = c->seq_ctrl.p; qa.mat = c->seq_mat.p; qa.flags = c->seq_flags.p;
-        size_t dyn = dyn_base;
-        const size_t sig_bytes = lds_slice(((size_t)c->sig_mask + 1) * 8) + lds_slice(((size_t)c->sig_mask + 1) * 4);
-        const size_t st_bytes = lds_slice((size_t)c->st_n * 8) + lds_slice((size_t)c->st_n * 32) + lds_slice(256 * 4);
-        const size_t room96 = dyn_room < 96 * 1024 ? dyn_room : 96 * 1024, room112 = dyn_room < 112 * 1024 ? dyn_room : 112 * 1024;
-        if (dyn + sig_bytes <= room96) { qa.lds_sigs = 1; dyn += sig_bytes; }
-        if (c->st_n && dyn + st_bytes <= room96) { qa.lds_states = 1; dyn += st_bytes; }
-        if (dyn + lds_slice(kChooseEntries) <= room112) { qa.lds_choose = 1; dyn += lds_slice(kChooseEntries); }
-        HIPCHK(c, hipFuncSetAttribute(any_g4 ? (const void*)k_decide<true> : (const void*)k_decide<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
-        if (any_g4) hipLaunchKernelGGL(k_decide<true>, dim3(1 + kWorkerBlocks), dim3(64 * kDecideWaves), dyn, c->streams.use(0), qa);
-        else hipLaunchKernelGGL(k_decide<false>, dim3(1 + kWorkerBlocks), dim3(64 * kDecideWaves), dyn, c->streams.use(0), qa);
-        HIPCHK(c, hipGetLastError());
-        uint32_t flags[4] = {0, 0, 0, 0};
-        HIPCHK(c, hipMemcpyAsync(flags, c->seq_flags.p, sizeof flags, hipMemcpyDeviceToHost, c->streams.use(0)));
-        HIPCHK(c, c->streams.wait(0));
-        if (tune_env("NHDFIT_SEQ_PROF")) {
-            uint32_t ctl[32];
-            HIPCHK(c, hipMemcpy(ctl, c->seq_ctrl.p, sizeof ctl, hipMemcpyDeviceToHost));
-            fprintf(stderr, "[nhdfit] k_decide: %u queue items; GPU-less pods: %u verifications failed, %u looked at a node in LDS, %u at a published one, "
-                            "%u at an untouched one, %u waited for an earlier pod's target, %u window rescans, %u sent back by the sequencer\n",
-                    ctl[1] ? ctl[1] - 1 : 0, ctl[4], ctl[5], ctl[6], ctl[7], ctl[8], ctl[14], ctl[15]);
-            fprintf(stderr, "[nhdfit] k_decide sequencer: waiting for fetchers %.2f ms, pods with GPUs %.2f ms, GPU-less pods: waiting for their speculators %.2f ms, "
-                            "validation %.2f ms\n", ctl[9] * 1e-5, ctl[10] * 1e-5, ctl[11] * 1e-5, ctl[12] * 1e-5);
-            fprintf(stderr, "[nhdfit] k_decide fetcher 0: waiting for list entries / windows %.2f ms, for the ring %.2f ms, issue + park %.2f ms\n", ctl[2] * 1e-5, ctl[3] * 1e-5, ctl[13] * 1e-5);
-            fprintf(stderr, "[nhdfit] k_decide sequencer, a pod with GPUs: window + pick %.2f ms, take %.2f ms, queue entry %.2f ms\n", ctl[28] * 1e-5, ctl[29] * 1e-5, ctl[30] * 1e-5);
-            fprintf(stderr, "[nhdfit] k_decide speculators, finer: candidate pick %.2f ms, pre-checks %.2f ms, NIC bits %.2f ms, (mapping = verification), before post %.2f ms, "
-                            "post + first-touch + result %.2f ms, (summary = stage 1)\n", ctl[23] * 1e-5, ctl[24] * 1e-5, ctl[25] * 1e-5, ctl[26] * 1e-5, ctl[27] * 1e-5);
-            fprintf(stderr, "[nhdfit] k_decide speculators (%d, summed): set-up %.2f ms, node state %.2f ms, verification %.2f ms, commit stage 1 %.2f ms, waiting (sequencer, earlier pods) %.2f ms, "
-                            "commit stage 2 %.2f ms, publication %.2f ms\n", kSpecWaves, ctl[16] * 1e-5, ctl[17] * 1e-5, ctl[18] * 1e-5, ctl[19] * 1e-5, ctl[20] * 1e-5, ctl[22] * 1e-5, ctl[21] * 1e-5);
-        }
-        if (flags[1] || flags[3]) {
-            // a NIC state without a signature id (or a wait that ran out): start over with the kernel whose stop / intern /
-            // resume protocol the caller knows
-            if ((rc = undo_all())) return rc;
-            if ((rc = reset_scan_state(false))) return rc;
-            fast = false;
+    if (engine) {
+        bool gave_back = false;
+        TRY(run_decision_engine(c, sa, lds, any_g4, gave_back));
+        if (gave_back) {                                        // start over with the general kernel
+            TRY(undo_batch(c, sa));
+            TRY(reset_scan_state(c, 0u));
+            engine = false;
         } else decided = P;
     }
-    if (!fast) {
-        if ((rc = run_general(nullptr, 0, decided))) return rc;
-    }
-    if (!apply) { if ((rc = undo_all())) return rc; }
-    c->seq_host.resize(P);
-    HIPCHK(c, hipMemcpyAsync(c->seq_host.data(), c->seq_out.p, P * sizeof(SeqResult), hipMemcpyDeviceToHost, c->streams.use(0)));
-    if (place_out) HIPCHK(c, hipMemcpyAsync(place_out, c->seq_place.p, (size_t)P * sizeof(nhdfit_placement), hipMemcpyDeviceToHost, c->streams.use(0)));
-    rc = nhdfit_sync(c);
-    if (rc) return rc;
+    if (!engine) TRY(run_general_kernel(c, sa, decided));
+    if (!apply) TRY(undo_batch(c, sa));
+    TRY(collect_seq_results(c, P, decided, apply, node_out, map_out, place_out, status_out));
     *n_done = decided;
-    int64_t lo = -1, hi = -1;
-    for (uint32_t i = 0; i < decided; ++i) {
-        const SeqResult& o = c->seq_host[i];
-        node_out[i] = o.node;
-        if (map_out) map_out[i] = o.map;
-        if (status_out) status_out[i] = o.status;
-        if (o.node >= 0) {
-            const int64_t v = o.node - (int64_t)c->global_base;
-            lo = lo < 0 || v < lo ? v : lo;
-            hi = v + 1 > hi ? v + 1 : hi;
-        }
-    }
-    if (apply && lo >= 0) {                                     // records of the committed nodes are stale
-        mark_records_stale(c, (uint32_t)lo, (uint32_t)hi);
-    }
     return NHDFIT_OK;
 }
 
@@ -2473,22 +2486,9 @@ int nhdfit_commit(nhdfit_ctx* c, uint32_t node, const nhdfit_req* req, const nhd
     if (!map->valid) return fail(c, NHDFIT_E_INVAL, "the mapping is not valid");
     if (!req_valid(*req)) return fail(c, NHDFIT_E_INVAL, "the request is not valid (map type NUMA / PCI, 1..%d proc groups)", NHDFIT_MAX_GROUPS);
     if (c->wide_slot(node) >= 0) return fail(c, NHDFIT_E_INVAL, "node %u is a wide node: its commit step is nhdfit_wide_commit", node);
-    for (uint32_t g = 0; g <= req->n_groups; ++g) {          // entries index two-element arrays / 16-entry NIC tables on the device
-        if (map->cpu[g] < 0 || map->cpu[g] >= NHDFIT_MAX_NUMA) return fail(c, NHDFIT_E_INVAL, "mapping: cpu[%u] = %d is not a NUMA node", g, (int)map->cpu[g]);
-        if (g == req->n_groups) break;
-        if (map->gpu[g] < 0 || map->gpu[g] >= NHDFIT_MAX_NUMA || map->nic_numa[g] < 0 || map->nic_numa[g] >= NHDFIT_MAX_NUMA)
-            return fail(c, NHDFIT_E_INVAL, "mapping: group %u sits on NUMA node %d / its NIC on %d", g, (int)map->gpu[g], (int)map->nic_numa[g]);
-        if (map->nic_idx[g] < 0 || map->nic_idx[g] >= NHDFIT_MAX_NICS_PER_NUMA)
-            return fail(c, NHDFIT_E_INVAL, "mapping: group %u uses NIC ordinal %d", g, (int)map->nic_idx[g]);
-    }
+    TRY(check_mapping(c, map, req->n_groups, NHDFIT_MAX_NUMA));
     HIPCHK(c, hipSetDevice(c->dev));
-    // the commit writes the planes: steps in flight on EITHER pipe (their fit roles, digests running ahead, pending mapping
-    // phases) read them - wait for both, as every other writer of the mirror does (nhdfit_upload_nodes)
-    // ... unless nothing can be in flight anywhere but on this very stream: no batch is staged (the single-launch finds leave none) and
-    // the ledger holds no mark for another pipe's stream or for the reduce stream - then stream order is all the commit needs (the
-    // scheduler's pod-at-a-time loop: asking the stream whether the find's launch has retired cost ~10 us per pod)
-    if (c->P || !c->streams.sides_clean()) TRY(sync_all(c));
-    else TRY(check_skipped_waits(c, "nhdfit_commit"));
+    TRY(writers_wait(c, "nhdfit_commit"));                 // the commit writes the planes
     if (!c->commit_host) return fail(c, NHDFIT_E_STATE, "no host block for the commit's result");
     CommitArgs ca;
     memset(&ca, 0, sizeof ca);
@@ -2527,9 +2527,7 @@ int nhdfit_find_commit(nhdfit_ctx* c, const nhdfit_req* req, double now, const u
     c->fc_composed++;
     if (rf == 1 && prev_node >= 0) {                            // (rf == 2: the launch has stored it)
         HIPCHK(c, hipSetDevice(c->dev));
-        // a writer of the mirror: as nhdfit_commit
-        if (c->P || !c->streams.sides_clean()) TRY(sync_all(c));
-        else TRY(check_skipped_waits(c, "nhdfit_find_commit"));
+        TRY(writers_wait(c, "nhdfit_find_commit"));             // the correction writes plane 4
         hipLaunchKernelGGL(k_set_busy, dim3(1), dim3(64), 0, c->streams.use(0), c->p4.p, (uint32_t)prev_node, prev_busy_time);   // (stream order: the find follows on pipe 0)
         HIPCHK(c, hipGetLastError());
         const uint32_t v = (uint32_t)prev_node;

@@ -9,15 +9,15 @@ starts with.  An island mask keeps the GPU nodes of one early chunk and one far 
 the island and must still be given the far node (Matcher.py:393-421), which some other block finds.
 
 The cuts, all computed on the host (nhd_amd/csrc/nhdfit.hip unless named otherwise; chunks = ceil(n / 64), tiles = ceil(P / 64)):
-  (a) build_items, :1118-1137.  rec_bytes = chunks * 64 * (16 * (max_wcls + 1) + 8); small_shard = rec_bytes <= 2 MiB - with pods of
+  (a) build_items, :1230-1255.  rec_bytes = chunks * 64 * (16 * (max_wcls + 1) + 8); small_shard = rec_bytes <= 2 MiB - with pods of
       all three row widths (max_wcls = 2) that is chunks <= 585.  by_xcd = chunks >= 32 * nw and (nw == 8 or the batch find) and not
       small_shard: every tile is cut at chunks * r / 8 (the step, nw = 8) or chunks * r / 16 (k_findn, nw = 4); otherwise at
       chunks * b / nb;
-  (b) enqueue_step, :1445.  geom_big = tiles * ceil(chunks / 32) >= CUs (256): the 512-thread form (nw = 8), the only one that takes (a)'s eighths;
-  (c) find_small, :1626.  k_find runs ceil(chunks / 32) fit blocks (at most one per CU);
-  (d) lone_find_args, :1547.  k_find1 / k_find1_commit run ceil(chunks / 8) blocks;
+  (b) enqueue_step, :1475.  geom_big = tiles * ceil(chunks / 32) >= CUs (256): the 512-thread form (nw = 8), the only one that takes (a)'s eighths;
+  (c) find_small, :1682.  k_find runs ceil(chunks / 32) fit blocks (at most one per CU);
+  (d) lone_find_args, :1598.  k_find1 / k_find1_commit run ceil(chunks / 8) blocks;
   (e) step_kernel.h:232.  k_rows_t turns the verdict matrix into rows by groups of 16 chunks;
-  (f) find_batch, :1770.  k_findn reads up to 512 requests from the host block and copies more;
+  (f) find_batch, :1798.  k_findn reads up to 512 requests from the host block and copies more;
   (g) explain_kernel.h:12.  16 pods per explain block.
 
 Rung  cfg      n  chunks  what it sits on
@@ -357,7 +357,7 @@ def explain_masks(r):
 
 def mask_sequence(r):
     """The rung's masks in turn, then one straddle mask twice and none: the small finds keep the mask they uploaded last and compare
-    the next one with it (upload_small_cand, nhdfit.hip:1555-1566)."""
+    the next one with it (upload_small_cand, nhdfit.hip:1606-1617)."""
     masks = r.masks()
     again = next(m for m in masks if m[0].startswith("straddle"))
     return masks + [again, again, masks[0]]
