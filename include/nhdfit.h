@@ -379,10 +379,13 @@ int nhdfit_set_dictionary(nhdfit_ctx* ctx, uint32_t max_cores_per_numa, uint32_t
  * index `global_base` (candidate order of the whole cluster; used for the score word).
  * Growing the capacity discards the mirror's contents (node count becomes 0). */
 int nhdfit_reserve_nodes(nhdfit_ctx* ctx, uint32_t capacity, uint64_t global_base);
-/* Full or delta upload of `count` node records starting at local index `first`. */
+/* Full or delta upload of `count` node records starting at local index `first`: inside the mirror, or appended to it - a slice
+ * that would leave a gap (`first` beyond the mirror's node count) is refused (NHDFIT_E_INVAL). */
 int nhdfit_upload_nodes(nhdfit_ctx* ctx, uint32_t first, uint32_t count,
                         const nhdfit_plane0* p0, const nhdfit_plane1* p1, const nhdfit_plane2* p2,
                         const nhdfit_plane3* p3, const nhdfit_plane4* p4, const nhdfit_detail* detail);
+/* Cut the mirror to its first `n_nodes` nodes: wide and origin records past the new end go with their nodes.  An empty mirror (0,
+ * or a capacity grown by nhdfit_reserve_nodes) also forgets the node classes interned for the nodes it held. */
 int nhdfit_set_node_count(nhdfit_ctx* ctx, uint32_t n_nodes);
 
 /* The wide records of the mirror's nodes [first, first + count): `n_wide` records (ascending `index`, each inside the range)

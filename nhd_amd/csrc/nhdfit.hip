@@ -834,68 +834,6 @@ int nhdfit_set_dictionary(nhdfit_ctx* c, uint32_t max_cores_per_numa, uint32_t m
     return NHDFIT_OK;
 }
 
-int nhdfit_reserve_nodes(nhdfit_ctx* c, uint32_t capacity, uint64_t global_base) {
-    if (!c) return NHDFIT_E_INVAL;
-    HIPCHK(c, hipSetDevice(c->dev));
-    TRY(sync_all(c));
-    if (capacity > c->capacity) {
-        c->n = 0;                                   // growing drops the contents: the caller re-uploads
-        c->n_wide = 0; c->wide_index.clear();
-        c->rec_all = true;
-        const size_t padded = ((size_t)capacity + 63) & ~size_t(63);       // the fit role reads whole 64-node chunks
-        HIPCHK(c, c->p0.reserve(padded)); HIPCHK(c, c->p1.reserve(padded)); HIPCHK(c, c->p2.reserve(padded));
-        HIPCHK(c, c->p3.reserve(padded)); HIPCHK(c, c->p4.reserve(padded)); HIPCHK(c, c->det.reserve(capacity));
-        HIPCHK(c, c->origin.reserve(capacity)); c->origin_hi = 0;
-        for (auto& r : c->rec) HIPCHK(c, r.reserve(padded));
-        for (auto& r : c->rec_bt) HIPCHK(c, r.reserve(padded));
-        HIPCHK(c, hipMemset(c->p4.p, 0, padded * sizeof(nhdfit_plane4)));   // busy times of the padding lanes: any finite value
-        c->capacity = capacity;
-    }
-    c->global_base = global_base;
-    return NHDFIT_OK;
-}
-
-int nhdfit_set_node_count(nhdfit_ctx* c, uint32_t n) {
-    if (!c) return NHDFIT_E_INVAL;
-    if (n > c->capacity) return fail(c, NHDFIT_E_INVAL, "node count %u exceeds reserved capacity %u", n, c->capacity);
-    if (n != c->n) {
-        HIPCHK(c, hipSetDevice(c->dev));
-        TRY(sync_all(c));     // mapping phases of steps in flight still read the old count
-        c->rec_all = true;                                  // the padding records of the last chunk move
-        c->n_items = 0;
-        c->n = n;
-        if (c->n_wide) {                                    // wide records past the new end go with their nodes
-            std::vector<nhdfit_wide_node> h(c->n_wide);
-            HIPCHK(c, hipMemcpy(h.data(), c->wide.p, h.size() * sizeof h[0], hipMemcpyDeviceToHost));
-            uint32_t keep = 0;
-            while (keep < c->n_wide && h[keep].index < n) ++keep;
-            c->n_wide = keep;
-            c->wide_index.resize(keep);
-        }
-    }
-    return NHDFIT_OK;
-}
-
-int nhdfit_upload_nodes(nhdfit_ctx* c, uint32_t first, uint32_t count, const nhdfit_plane0* p0, const nhdfit_plane1* p1,
-                        const nhdfit_plane2* p2, const nhdfit_plane3* p3, const nhdfit_plane4* p4, const nhdfit_detail* det) {
-    if (!c) return NHDFIT_E_INVAL;
-    if (!count) return NHDFIT_OK;
-    if (!p0 || !p1 || !p2 || !p3 || !p4 || !det) return fail(c, NHDFIT_E_INVAL, "NULL plane");
-    if ((uint64_t)first + count > c->capacity) return fail(c, NHDFIT_E_INVAL, "upload [%u,%u) exceeds capacity %u", first, first + count, c->capacity);
-    HIPCHK(c, hipSetDevice(c->dev));
-    TRY(sync_all(c));     // a step in flight must not see a half-written record
-    if (first + count > c->n) { c->rec_all = true; c->n_items = 0; }   // the node count changes: the last chunk's padding moves
-    else mark_records_stale(c, first, first + count);
-    HIPCHK(c, hipMemcpy(c->p0.p + first, p0, count * sizeof *p0, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->p1.p + first, p1, count * sizeof *p1, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->p2.p + first, p2, count * sizeof *p2, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->p3.p + first, p3, count * sizeof *p3, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->p4.p + first, p4, count * sizeof *p4, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->det.p + first, det, count * sizeof *det, hipMemcpyHostToDevice));
-    if (first + count > c->n) c->n = first + count;
-    return NHDFIT_OK;
-}
-
 namespace {
 // Tile-image layouts for the current dictionary, a batch of P pods and the provisioned X rows; (re)sizes the image buffers for P pods.
 int refresh_layouts(nhdfit_ctx* c, uint32_t P) {
@@ -954,6 +892,92 @@ int refresh_layouts(nhdfit_ctx* c, uint32_t P) {
     return NHDFIT_OK;
 }
 
+// The mirror has become empty (every stream has been waited for, rec_all is set): the node classes interned for its nodes go with
+// them.  A class key embeds signature ids of the dictionary it was interned under - the next cluster may bring a smaller one, and
+// the digest role forms an X row per class whether a node still names it or not - and the classes of departed clusters would count
+// towards kXSlots / 2 and hold x_cap, with it every tile's hot section, at the largest cluster's size for good.  Where x_cap moves,
+// what ensure_records redoes when it grows is redone here.  (A dictionary that grows under a live mirror keeps its classes.)
+int forget_classes(nhdfit_ctx* c) {
+    HIPCHK(c, hipMemsetAsync(c->xkeys.p, 0, kXSlots * sizeof(unsigned long long), c->streams.use(0)));
+    HIPCHK(c, hipMemsetAsync(c->xids.p, 0xFF, kXSlots * sizeof(uint32_t), c->streams.use(0)));
+    HIPCHK(c, hipMemsetAsync(c->xnx.p, 0, 2 * sizeof(uint32_t), c->streams.use(0)));
+    c->nx = c->sig_use_nx = c->n_sig_use = 0;
+    if (c->x_cap != kMinXCap) {
+        c->x_cap = kMinXCap;
+        for (Pipe& p : c->pipe) p.n_dig = std::min(p.n_dig, p.n_fit);   // every staged table image is redone
+        TRY(refresh_layouts(c, c->P));
+    }
+    return NHDFIT_OK;
+}
+}  // namespace
+
+int nhdfit_reserve_nodes(nhdfit_ctx* c, uint32_t capacity, uint64_t global_base) {
+    if (!c) return NHDFIT_E_INVAL;
+    HIPCHK(c, hipSetDevice(c->dev));
+    TRY(sync_all(c));
+    if (capacity > c->capacity) {
+        c->n = 0;                                   // growing drops the contents: the caller re-uploads
+        c->n_wide = 0; c->wide_index.clear();
+        c->rec_all = true;
+        TRY(forget_classes(c));
+        const size_t padded = ((size_t)capacity + 63) & ~size_t(63);       // the fit role reads whole 64-node chunks
+        HIPCHK(c, c->p0.reserve(padded)); HIPCHK(c, c->p1.reserve(padded)); HIPCHK(c, c->p2.reserve(padded));
+        HIPCHK(c, c->p3.reserve(padded)); HIPCHK(c, c->p4.reserve(padded)); HIPCHK(c, c->det.reserve(capacity));
+        HIPCHK(c, c->origin.reserve(capacity)); c->origin_hi = 0;
+        for (auto& r : c->rec) HIPCHK(c, r.reserve(padded));
+        for (auto& r : c->rec_bt) HIPCHK(c, r.reserve(padded));
+        HIPCHK(c, hipMemset(c->p4.p, 0, padded * sizeof(nhdfit_plane4)));   // busy times of the padding lanes: any finite value
+        c->capacity = capacity;
+    }
+    c->global_base = global_base;
+    return NHDFIT_OK;
+}
+
+int nhdfit_set_node_count(nhdfit_ctx* c, uint32_t n) {
+    if (!c) return NHDFIT_E_INVAL;
+    if (n > c->capacity) return fail(c, NHDFIT_E_INVAL, "node count %u exceeds reserved capacity %u", n, c->capacity);
+    if (n != c->n) {
+        HIPCHK(c, hipSetDevice(c->dev));
+        TRY(sync_all(c));     // mapping phases of steps in flight still read the old count
+        c->rec_all = true;                                  // the padding records of the last chunk move
+        c->n_items = 0;
+        c->n = n;
+        c->origin_hi = std::min(c->origin_hi, n);           // origin records past the new end go with their nodes, as the wide ones do
+        if (!n) TRY(forget_classes(c));
+        if (c->n_wide) {                                   // wide records past the new end go with their nodes
+            std::vector<nhdfit_wide_node> h(c->n_wide);
+            HIPCHK(c, hipMemcpy(h.data(), c->wide.p, h.size() * sizeof h[0], hipMemcpyDeviceToHost));
+            uint32_t keep = 0;
+            while (keep < c->n_wide && h[keep].index < n) ++keep;
+            c->n_wide = keep;
+            c->wide_index.resize(keep);
+        }
+    }
+    return NHDFIT_OK;
+}
+
+int nhdfit_upload_nodes(nhdfit_ctx* c, uint32_t first, uint32_t count, const nhdfit_plane0* p0, const nhdfit_plane1* p1,
+                        const nhdfit_plane2* p2, const nhdfit_plane3* p3, const nhdfit_plane4* p4, const nhdfit_detail* det) {
+    if (!c) return NHDFIT_E_INVAL;
+    if (!count) return NHDFIT_OK;
+    if (!p0 || !p1 || !p2 || !p3 || !p4 || !det) return fail(c, NHDFIT_E_INVAL, "NULL plane");
+    if ((uint64_t)first + count > c->capacity) return fail(c, NHDFIT_E_INVAL, "upload [%u,%u) exceeds capacity %u", first, first + count, c->capacity);
+    if (first > c->n) return fail(c, NHDFIT_E_INVAL, "node records [%u,%u) are missing", c->n, first);
+    HIPCHK(c, hipSetDevice(c->dev));
+    TRY(sync_all(c));     // a step in flight must not see a half-written record
+    if (first + count > c->n) { c->rec_all = true; c->n_items = 0; }   // the node count changes: the last chunk's padding moves
+    else mark_records_stale(c, first, first + count);
+    HIPCHK(c, hipMemcpy(c->p0.p + first, p0, count * sizeof *p0, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->p1.p + first, p1, count * sizeof *p1, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->p2.p + first, p2, count * sizeof *p2, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->p3.p + first, p3, count * sizeof *p3, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->p4.p + first, p4, count * sizeof *p4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->det.p + first, det, count * sizeof *det, hipMemcpyHostToDevice));
+    if (first + count > c->n) c->n = first + count;
+    return NHDFIT_OK;
+}
+
+namespace {
 // The order a call's pods are staged in (perm[k] = caller's index of the pod at device position k): a function of the requests
 // alone.  It is also the order in which EVERY form of a sharded find hands its score words to the all-reduce - the staged step and
 // the single-launch find alike - so that ranks that take different forms for the same call (one shard holds a wide node, spilled

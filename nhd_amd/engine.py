@@ -3,6 +3,7 @@ from __future__ import annotations
 
 import ctypes
 import operator
+import weakref
 from typing import Optional, Tuple
 
 import numpy as np
@@ -29,9 +30,11 @@ class Engine:
         self.ctx = h
         self.device = device
         self.n = 0
+        self.capacity = 0                # what nhdfit_reserve_nodes has been asked for so far (it only grows)
         self.P = 0
         self.global_base = 0
         self._dict_version = -1
+        self._dict_of = None             # the packer that version belongs to (weakly held)
         self.n_wide = 0
 
     def close(self):
@@ -50,7 +53,8 @@ class Engine:
 
     # ---- state ------------------------------------------------------------------------
     def set_dictionary(self, packer: pack.Packer):
-        if self._dict_version == packer.dict_version:
+        # (the version counts one packer's growth: two packers may well stand at the same count with different dictionaries)
+        if self._dict_version == packer.dict_version and self._dict_of is not None and self._dict_of() is packer:
             return
         caps, sig_off, pool_off, glimit, cc, ncls, nsig, npools, ncc = packer.dictionary_arrays()
         gs = packer.group_set_array()
@@ -58,6 +62,7 @@ class Engine:
                                                  _p(gs), len(packer.group_sets), _p(caps), ncls, _p(sig_off), nsig, _p(pool_off), _p(glimit),
                                                  npools, _p(cc), ncc))
         self._dict_version = packer.dict_version
+        self._dict_of = weakref.ref(packer)
 
     def forget_dictionary(self):
         """The next set_dictionary uploads whatever packer it is given (a NEW Packer restarts its version count)."""
@@ -77,7 +82,15 @@ class Engine:
             missing = next(i for i in range(table.n) if i not in table.share)
             raise _lib.NhdFitError(-5, "ENABLE_SHARING: node %d of the uploaded slice carries no speed_used record" % (first + missing))
         cap = max(capacity or 0, first + table.n)
+        if first > self.n:
+            # (nhdfit_upload_nodes refuses it too: nothing has been written to the nodes in between)
+            raise _lib.NhdFitError(-1, "node records [%d,%d) are missing" % (self.n, first))
+        if first > 0 and cap > self.capacity:
+            # growing the capacity discards the mirror's contents: the slice would stand behind nodes that are gone
+            raise _lib.NhdFitError(-1, "a slice at %d that grows the capacity from %d to %d would discard the nodes in front of it: "
+                                   "upload the whole table" % (first, self.capacity, cap))
         self._chk(self.lib.nhdfit_reserve_nodes(self.ctx, cap, global_base))
+        self.capacity = max(self.capacity, cap)
         arrs = [np.ascontiguousarray(x) for x in (table.p0, table.p1, table.p2, table.p3, table.p4, table.detail)]
         self._chk(self.lib.nhdfit_upload_nodes(self.ctx, first, table.n, *[_p(a) for a in arrs]))
         if table.origin is not None and table.n:
@@ -170,6 +183,21 @@ class Engine:
             self._share = None
         self.n = 0
         self.n_wide = 0
+
+    def truncate(self, n: int):
+        """The mirror cut to its first `n` nodes (nhdfit_set_node_count): wide, speed_used and origin records past the new end go with
+        their nodes; truncate(0) is reset_nodes()."""
+        n = int(n)
+        if n == 0:
+            return self.reset_nodes()
+        if n > self.n:
+            raise _lib.NhdFitError(-1, "truncate(%d) of a mirror of %d nodes" % (n, self.n))
+        self._chk(self.lib.nhdfit_set_node_count(self.ctx, n))
+        self.n = n
+        if self.n_wide:
+            self.n_wide = self.wide_count()
+        if getattr(self, "_share", None) is not None:
+            self._share = self._share[:n].copy()          # (the device keeps the prefix of its own records, commits included)
 
     def set_outputs(self, bitmap=True, mapping=True):
         self._chk(self.lib.nhdfit_set_outputs(self.ctx, int(bitmap), int(mapping)))
@@ -434,9 +462,11 @@ class _ShardView(Engine):
         self.ctx = ctypes.c_void_p(ctx)
         self.device = device
         self.n = 0
+        self.capacity = 0
         self.P = 0
         self.global_base = 0
         self._dict_version = -1
+        self._dict_of = None
         self.n_wide = 0
 
     def close(self):

@@ -360,17 +360,23 @@ def oracle_schedule_one(descs, specs):
     return out
 
 
-def check_schedule_one(matcher_factory, seed, fused_form):
+def check_schedule_one(matcher_factory, seed, fused_form, matcher=None):
     """ScheduleOne in attached mode, pod after pod, the placements applied with the stand-in's mutators: result and placement record
     of every pod against the oracle's FindNode + commit on a second copy, mirror == objects at the end.  fused_form: the engine has
     nhdfit_find_commit - then find_commit_counts() must say that every pod of at most three groups took the ONE launch (no commit
     in the loop is one the reference raises on: the loop ends in front of the first), a four-group pod the composed form inside
-    the library, and a pod of the general path neither (HipMatcher composes it)."""
+    the library, and a pod of the general path neither (HipMatcher composes it).  `matcher`: a matcher that has been in use (detached;
+    it is given this case's clock and attached to this case's nodes) instead of a new one - its counters move as a new one's do."""
     descs, specs = schedule_one_case(seed)
     want = oracle_schedule_one(descs, specs)
     clock = sched_check.Clock(NOW)
     nl = sched_standin.adopt(util.build_cluster(descs), clock)
-    m = matcher_factory(clock)
+    if matcher is None:
+        m = matcher_factory(clock)
+    else:
+        m = matcher
+        m.clock = clock
+    base = m.engine.find_commit_counts() if fused_form else None
     m.attach(nl)
     assert m.wide_nodes == [] and not m.unmirrored
     words, sigs = dict_stream(util.build_cluster(descs))
@@ -397,7 +403,8 @@ def check_schedule_one(matcher_factory, seed, fused_form):
     assert sched_check.mirror_state(m) == sched_check.packed(nl)
     out = {"seed": seed, "pods": len(want), "placed": placed, "placed on 33..64-core nodes": on_upper}
     if fused_form:
-        assert m.engine.find_commit_counts() == (fused_want, composed_want) and fused_want > 0
+        end = m.engine.find_commit_counts()
+        assert (end[0] - base[0], end[1] - base[1]) == (fused_want, composed_want) and fused_want > 0
         out.update({"fused": fused_want, "composed": composed_want})
     return out
 

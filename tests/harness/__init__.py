@@ -389,6 +389,8 @@ class HarnessEngine:
     def __init__(self, device=0):
         self.device = device
         self.n = 0
+        self.capacity = 0                               # Engine.capacity: it only grows
+        self.origin_hi = 0                              # nhdfit_ctx::origin_hi: origin records [0, origin_hi) are there
         self.global_base = 0
         self.packer = None
         self.table = None
@@ -408,6 +410,12 @@ class HarnessEngine:
             out[k] = self.wide[i]
             out[k]["index"] = i
         return out
+
+    def wide_count(self):
+        return len(self.wide)
+
+    def wide_download(self):
+        return self._wide_records()
 
     def _share_records(self):
         """The speed_used records in the order of _wide_records(), or None (shipped arithmetic)."""
@@ -431,10 +439,27 @@ class HarnessEngine:
 
     def reset_nodes(self):
         self.n = 0
+        self.origin_hi = 0                              # (nhdfit_set_node_count clamps it to the new count)
         self.table = None
         self.wide = {}
         self.share = {}
         self.sharing = False
+
+    def truncate(self, n):
+        """Engine.truncate: the mirror cut to its first n nodes; wide, speed_used and origin records past the new end go with them."""
+        from nhd_amd._lib import NhdFitError
+        n = int(n)
+        if n == 0:
+            return self.reset_nodes()
+        if n > self.n:
+            raise NhdFitError(-1, "truncate(%d) of a mirror of %d nodes" % (n, self.n))
+        self.table = self.table.slice(0, n)
+        self.table = pack.NodeTable(list(self.table.names), *[np.array(getattr(self.table, f)) for f in
+                                                              ("p0", "p1", "p2", "p3", "p4", "detail", "origin")])
+        self.n = n
+        self.origin_hi = min(self.origin_hi, n)
+        self.wide = {i: r for i, r in self.wide.items() if i < n}
+        self.share = {i: r for i, r in self.share.items() if i < n}
 
     def upload(self, table, global_base=0, first=0, capacity=None):
         from nhd_amd._lib import NhdFitError
@@ -443,6 +468,16 @@ class HarnessEngine:
             raise NhdFitError(-5, "ENABLE_SHARING: the uploaded slice [%d, %d) carries no speed_used records" % (first, first + table.n))
         if table.share and len(table.share) != table.n:
             raise NhdFitError(-5, "ENABLE_SHARING: a node of the uploaded slice carries no speed_used record")
+        cap = max(capacity or 0, first + table.n)
+        if first > self.n:                                    # Engine.upload's refusals of a gap, before anything changes
+            raise NhdFitError(-1, "node records [%d,%d) are missing" % (self.n, first))
+        if first > 0 and cap > self.capacity:
+            raise NhdFitError(-1, "a slice at %d that grows the capacity from %d to %d would discard the nodes in front of it: "
+                              "upload the whole table" % (first, self.capacity, cap))
+        if cap > self.capacity:                               # nhdfit_reserve_nodes: growing drops the contents
+            self.reset_nodes()
+            self.capacity = cap
+            whole = True
         if table.share:
             self.sharing = True
         if whole:
@@ -450,8 +485,17 @@ class HarnessEngine:
                                                             ("p0", "p1", "p2", "p3", "p4", "detail")],
                                         np.zeros(table.n, pack.ORIGIN) if table.origin is None else np.array(table.origin))
         else:
+            if first + table.n > self.n:                      # appended within the capacity: the node count grows
+                grown = pack.empty_table(first + table.n)
+                grown.origin = np.zeros(first + table.n, pack.ORIGIN)
+                for f in ("p0", "p1", "p2", "p3", "p4", "detail", "origin"):
+                    getattr(grown, f)[:self.n] = getattr(self.table, f)
+                grown.names = list(self.table.names) + list(table.names)[self.n - first:]
+                self.table = grown
             for f in ("p0", "p1", "p2", "p3", "p4", "detail") + (("origin",) if table.origin is not None else ()):
                 getattr(self.table, f)[first:first + table.n] = getattr(table, f)
+        if table.origin is not None and table.n:              # nhdfit_upload_origin
+            self.origin_hi = max(self.origin_hi, first + table.n)
         self.n = self.table.n
         self.global_base = global_base
         for i in [i for i in self.wide if first <= i < first + table.n]:      # nhdfit_wide_upload: the range's records are replaced
@@ -573,6 +617,9 @@ class HarnessEngine:
         return big_commit(self.packer, self.table, node, req, mapping, busy_time)[1]
 
     def apply_deltas(self, deltas):
+        if len(deltas) and self.origin_hi < self.n:
+            from nhd_amd._lib import NhdFitError
+            raise NhdFitError(-5, "upload the origin records first (nhdfit_upload_origin)")
         return apply_deltas(self.packer, self.table, deltas)
 
     def download(self, first=0, count=None):
