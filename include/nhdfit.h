@@ -662,6 +662,49 @@ int nhdfit_headroom_limits(nhdfit_ctx* ctx, const nhdfit_req* reqs, uint32_t P, 
 int nhdfit_group_headroom_limits(nhdfit_group* g, const nhdfit_req* reqs, uint32_t P, const uint64_t* const* cand, uint32_t max_per_node,
                                  nhdfit_headroom_sum* sum_out, uint16_t* const* counts_out, uint32_t* limits_out, uint8_t* const* stage_out);
 
+/* ---- candidates: the first K nodes FindNode would pick, in the order it would get there ------------------------------
+ * Matcher.SelectNode (nhd/Matcher.py:393-421) is a deterministic first-fit: the first feasible node in the order of `nl`, for a pod
+ * without GPUs the first feasible node without GPUs.  AttemptScheduling unwinds when SetPhysicalIdsFromMapping fails
+ * (nhd/NHDScheduler.py:291-299), when the NAD or annotation writes fail (:310-335) or when BindPodToNode fails (:340-345) - and the
+ * next FindNode on the same cluster names the same node again.  This call answers "where else":
+ *     candidates[0] is nhdfit_find's answer for the pod - score word and mapping bit for bit;
+ *     candidates[j] is what Matcher().FindNode answers for the pod on `nl` without the j nodes named before it: for a pod that
+ *     requests GPUs the feasible nodes in index order; for one without, the feasible nodes with GetTotalGPUs() == 0 in index order,
+ *     then the other feasible nodes in index order - descending score word.  Each entry's mapping is the one FindNode gives for that
+ *     node alone (GetNumaGroupIdx, nhd/Matcher.py:423-452, reads only that node's state, CPython set order included).
+ * "Feasible" is nhdfit_find's verdict bit: maintenance, hugepages, IsBusy against the busy window at `now` for pods that request
+ * GPUs, InitialNodeFilter under NHDFIT_RF_INITIAL_FILTER, `cand`.  A request of an invalid map type has no candidates.
+ * A candidate the mirror holds as a wide record is counted in not_evaluated and not listed (nhdfit_headroom's precedent): the list
+ * then ranks the nodes of the planes only, and not_evaluated != 0 says so.
+ * Nothing is written: not the mirror, busy times, staged batch or nhdfit_get_stats. */
+typedef struct {
+    uint64_t score;                             /* as score_out of nhdfit_find: the node is NHDFIT_SCORE_INDEX(score) - global_base   */
+    nhdfit_mapping map;
+    uint32_t reserved;
+} nhdfit_candidate;                             /* 32 bytes */
+#define NHDFIT_CANDIDATES_MAX_K       64u
+#define NHDFIT_CANDIDATES_FORM_WAVE    1u       /* the wavefront instantiation answered (pods of 1..3 processing groups)              */
+#define NHDFIT_CANDIDATES_FORM_GENERIC 2u       /* the instantiation with the generic set model (four processing groups)             */
+typedef struct {
+    uint32_t feasible;                          /* feasible nodes of the planes: the FITS bin of nhdfit_explain, the popcount of the
+                                                   pod's bitmap_out row                                                              */
+    uint32_t preferred;                         /* those of them without GPUs, for a pod without GPUs; 0 otherwise                    */
+    uint32_t returned;                          /* min(K, feasible): entries of the pod's list                                        */
+    uint32_t not_evaluated;                     /* candidates held as wide records: counted, not listed                               */
+    uint32_t form;                              /* NHDFIT_CANDIDATES_FORM_*; 0: nothing was launched (an empty mirror)                */
+    uint32_t reserved[3];
+} nhdfit_candidates_sum;                        /* 32 bytes */
+/* sum_out [P]; out [P][K], a pod's entries past `returned` all zero.  K: 1..NHDFIT_CANDIDATES_MAX_K (NHDFIT_E_INVAL otherwise, or
+ * for a NULL context).  cand as nhdfit_find.  nhdfit_big_req pods have no entry here.  NHDFIT_E_LIMIT as nhdfit_headroom: a
+ * dictionary of more than 4096 NIC signatures, a hugepage request beyond the pod tile's. */
+int nhdfit_candidates(nhdfit_ctx* ctx, const nhdfit_req* reqs, uint32_t P, double now, const uint64_t* cand, uint32_t K,
+                      nhdfit_candidates_sum* sum_out, nhdfit_candidate* out);
+/* ... over every shard of a group: the shards' lists merged per pod by descending score, the sums added (`returned`:
+ * min(K, feasible) of the sum; `form`: the larger).  owner_out: NULL, or [P][K] the shard of each entry (-1 past `returned`).
+ * cand as nhdfit_group_find. */
+int nhdfit_group_candidates(nhdfit_group* g, const nhdfit_req* reqs, uint32_t P, double now, const uint64_t* const* cand, uint32_t K,
+                            nhdfit_candidates_sum* sum_out, nhdfit_candidate* out, int32_t* owner_out);
+
 /* ---- request digest straight from the wire format (host code, no GPU needed) -------------------------
  * The pod's Triad libconfig text -> nhdfit_req, replacing TriadCfgParser(text, False).CfgToTopology(False)
  * (nhd/TriadCfgParser.py:337-380, called from nhd/NHDScheduler.py:262-270) followed by the getters FindNode

@@ -1,0 +1,42 @@
+// candidates_merge.h - how a shard's candidate lists go into the group's.  Host code: libnhdfit.so's group entry
+// (nhdfit_group_candidates) and the host twin (tests/harness/candidates_twin.cpp exports it) read the rule here;
+// nhd_amd/sharding.py states it once more for one process per GPU (merge_candidates), and tests/test_candidates_host_logic.py holds
+// the two to each other.
+#pragma once
+#include <stdint.h>
+#include <string.h>
+#include <algorithm>
+#include "../../include/nhdfit.h"
+
+namespace nhdfit {
+
+// One more shard (`shard`, its sums `part` [P] and lists `part_list` [P][K]) into the group's answer so far.  Per pod: the two lists
+// - each in descending score, the selection order (fit_core.h score_of: preferred nodes first, then ascending global index) - are
+// merged by descending score and cut at K; a score names one node of one shard, so no two entries tie.  Counts add; `returned` is
+// min(K, feasible) of the sum; the instantiation (`form`) takes the larger.  owner (optional, [P][K]): the shard of each entry, -1
+// past `returned`.  The caller starts from all-zero sums and lists (owner: -1).
+inline void merge_candidate_lists(nhdfit_candidates_sum* sum, nhdfit_candidate* list, int32_t* owner, const nhdfit_candidates_sum* part,
+                                  const nhdfit_candidate* part_list, uint32_t P, uint32_t K, int32_t shard) {
+    nhdfit_candidate row[NHDFIT_CANDIDATES_MAX_K];
+    int32_t own[NHDFIT_CANDIDATES_MAX_K];
+    for (uint32_t p = 0; p < P; ++p) {
+        nhdfit_candidates_sum& s = sum[p];
+        nhdfit_candidate* a = list + (size_t)p * K;
+        const nhdfit_candidate* b = part_list + (size_t)p * K;
+        int32_t* o = owner ? owner + (size_t)p * K : nullptr;
+        const uint32_t na = s.returned, nb = part[p].returned;
+        uint32_t i = 0, j = 0, k = 0;
+        while (k < K && (i < na || j < nb)) {
+            const bool take_a = j >= nb || (i < na && a[i].score > b[j].score);
+            own[k] = take_a ? (o ? o[i] : -1) : shard;
+            row[k++] = take_a ? a[i++] : b[j++];
+        }
+        memcpy(a, row, (size_t)k * sizeof *a);
+        if (o) memcpy(o, own, (size_t)k * sizeof *o);
+        s.feasible += part[p].feasible; s.preferred += part[p].preferred; s.not_evaluated += part[p].not_evaluated;
+        s.returned = std::min(K, s.feasible);
+        s.form = std::max(s.form, part[p].form);
+    }
+}
+
+}  // namespace nhdfit

@@ -38,6 +38,7 @@
 #include "dict_stream.h"
 #include "host_streams.h"
 #include "headroom_merge.h"
+#include "candidates_merge.h"
 
 using namespace nhdfit;
 
@@ -66,6 +67,7 @@ namespace {
 #include "big_kernel.h"
 #include "explain_kernel.h"
 #include "headroom_kernel.h"
+#include "candidates_kernel.h"
 #include "limit_kernel.h"
 #include "wide_room_kernel.h"
 
@@ -155,7 +157,7 @@ struct Pipe {                            // one software pipeline of steps: its 
 };
 
 // Buffers of the query entries - nhdfit_explain / _big (explain_kernel.h), nhdfit_headroom (headroom_kernel.h), _limits
-// (limit_kernel.h), _general (wide_room_kernel.h).  One set for all of them: a query waits for its own results before it returns.
+// (limit_kernel.h), _general (wide_room_kernel.h), nhdfit_candidates (candidates_kernel.h).  One set for all of them: a query waits for its own results before it returns.
 struct QueryBufs {
     DevBuf<nhdfit_req> reqs; DevBuf<nhdfit_big_req> big_reqs;   // the call's requests, by record type
     DevBuf<uint64_t> cand;                                       // [chunks] the call's candidate mask
@@ -165,6 +167,8 @@ struct QueryBufs {
     DevBuf<uint32_t> tickets; DevBuf<HeadroomSum> sum; DevBuf<uint16_t> counts;      // headroom: ticket counters, summary records, entries
     DevBuf<HeadroomFinal> final;                                 // limits: the runs' final states, a slab of templates at a time
     DevBuf<uint32_t> wide_tickets;                               // general: the wide launch's ticket counters, and behind them its flag words
+    DevBuf<uint32_t> cand_work;                                  // candidates: ticket counters, summary records and the blocks' records (one memset)
+    DevBuf<nhdfit_candidate> cand_out;                           // candidates: [P][K] entries
 };
 
 // Buffers of mode B (nhdfit_schedule_batch; seq_kernel.h, seq2_kernel.h): sized for one batch of P pods on n nodes by one reserve.
@@ -3161,6 +3165,89 @@ int nhdfit_group_headroom_limits(nhdfit_group* g, const nhdfit_req* reqs, uint32
         const int rc = nhdfit_headroom_limits(c, reqs, P, shard_ptr(cand, k), max_per_node, part.data(), shard_ptr(counts_out, k), hist.data(),
                                               shard_ptr(stage_out, k));
         if (!rc) { merge_headroom_sums(sum_out, part.data(), P); add_counts(limits_out, hist); }
+        return rc;
+    });
+}
+
+// ---- candidates: the first K nodes FindNode would pick, each with its mapping (candidates_kernel.h) ---------------------------------
+int nhdfit_candidates(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, double now, const uint64_t* cand, uint32_t K,
+                      nhdfit_candidates_sum* sum_out, nhdfit_candidate* out) {
+    if (!c) return NHDFIT_E_INVAL;
+    if (!reqs || !P || !sum_out || !out) return fail(c, NHDFIT_E_INVAL, "candidates: requests, sum_out and out are required");
+    if (!K || K > NHDFIT_CANDIDATES_MAX_K) return fail(c, NHDFIT_E_INVAL, "candidates: K is %u (1 .. %u)", K, (unsigned)NHDFIT_CANDIDATES_MAX_K);
+    for (uint32_t p = 0; p < P; ++p)
+        if (reqs[p].hugepages_gb > kMaxHpRows - 2) return fail(c, NHDFIT_E_LIMIT, "pod %u asks for %d GB of hugepages (<= %d)", p, reqs[p].hugepages_gb, kMaxHpRows - 2);
+    memset(sum_out, 0, (size_t)P * sizeof *sum_out);
+    memset(out, 0, (size_t)P * K * sizeof *out);
+    const uint32_t n = c->n;
+    if (!n) return NHDFIT_OK;
+    if (!c->ncls || !c->nsig) return fail(c, NHDFIT_E_STATE, "set the dictionary first (nhdfit_set_dictionary)");
+    if (!c->flat_words || c->nsig > kLoneMaxSigs)
+        return fail(c, NHDFIT_E_LIMIT, "candidates: the dictionary has %u NIC signatures (<= %u, in a stream of at most 65535 words)", c->nsig, kLoneMaxSigs);
+    QueryBufs& q = c->q;
+    TRY(stage_query(c, q.reqs, reqs, P, cand));
+    const uint32_t chunks = (n + 63) / 64;
+    CandArgs a;
+    memset(&a, 0, sizeof a);
+    a.p0 = c->p0.p; a.p1 = c->p1.p; a.p2 = c->p2.p; a.p3 = c->p3.p; a.p4 = c->p4.p; a.det = c->det.p; a.n = n;
+    a.global_base = c->global_base;
+    a.wide = c->wide.p; a.n_wide = c->n_wide;
+    a.d = DictView{c->caps.p, c->ncls, c->group_sets.p, SigDict{c->sig_off.p, c->pool_off.p, c->pool_glimit.p, c->cc.p, c->nsig}, c->sig_flat.p, c->flat_words, nullptr, 0};
+    a.nsig = c->nsig; a.fc_dim = c->max_cores + 1; a.fg_dim = c->max_gpus + 1; a.ngs = c->ngs;
+    const ShapeArgs sh = make_shape_args(c, c->pipe[0], 0);
+    a.mt = MapTables{sh.asc, sh.choose_tab, sh.st};
+    a.ncls = c->ncls;
+    a.busy_from = busy_threshold(now);
+    a.cand = cand ? q.cand.p : nullptr;
+    a.chunks = chunks; a.K = K;
+    a.all_generic = a.mt.choose_tab && a.mt.st.info ? 0u : 1u;
+    std::vector<uint32_t> form(P);
+    for (uint32_t p = 0; p < P; ++p)
+        form[p] = a.all_generic || (req_valid(reqs[p]) && reqs[p].n_groups > 3) ? NHDFIT_CANDIDATES_FORM_GENERIC : NHDFIT_CANDIDATES_FORM_WAVE;
+    // blocks per pod: two chunks per wavefront as k_find1, the chip's block slots shared out among the pods of a launch
+    const uint32_t slab = std::min(P, 65535u);                           // (gridDim.y)
+    const uint32_t slots = 4u * (uint32_t)c->prop.multiProcessorCount;
+    const uint32_t nb = std::max(1u, std::min((chunks + 7) / 8, (slots + slab - 1) / slab));
+    // the call's scratch in one block, zeroed by one memset: tickets [P] (padded to 16 bytes), summary records [P], block records [P][nb]
+    const size_t tick_words = ((size_t)P + 3) & ~size_t(3), sum_words = (size_t)P * (sizeof(CandSum) / 4), rec_words = (size_t)P * nb * cand_rec_words(K);
+    const size_t work_words = (tick_words + sum_words + rec_words + 3) & ~size_t(3);
+    HIPCHK(c, q.cand_work.reserve(work_words));
+    HIPCHK(c, q.cand_out.reserve((size_t)P * K));
+    HIPCHK(c, hipMemsetAsync(q.cand_work.p, 0, work_words * sizeof(uint32_t), c->streams.use(0)));
+    HIPCHK(c, hipMemsetAsync(q.cand_out.p, 0, (size_t)P * K * sizeof(nhdfit_candidate), c->streams.use(0)));
+    CandSum* dsum = reinterpret_cast<CandSum*>(q.cand_work.p + tick_words);
+    for (uint32_t t0 = 0; t0 < P; t0 += slab) {                          // (more pods than gridDim.y allows: in slabs)
+        const uint32_t S = std::min(slab, P - t0);
+        bool any_wave = false, any_g4 = false;
+        for (uint32_t p = t0; p < t0 + S; ++p) (form[p] == NHDFIT_CANDIDATES_FORM_GENERIC ? any_g4 : any_wave) = true;
+        a.reqs = q.reqs.p + t0; a.tickets = q.cand_work.p + t0; a.sum = dsum + t0;
+        a.recs = q.cand_work.p + tick_words + sum_words + (size_t)t0 * nb * cand_rec_words(K);
+        a.out = q.cand_out.p + (size_t)t0 * K;
+        if (any_wave) hipLaunchKernelGGL(k_cand_list<false>, dim3(nb, S), dim3(kCandBlock), kCandLds, c->streams.use(0), a);
+        HIPCHK(c, hipGetLastError());
+        if (any_g4) hipLaunchKernelGGL(k_cand_list<true>, dim3(nb, S), dim3(kCandBlock), kCandLds, c->streams.use(0), a);
+        HIPCHK(c, hipGetLastError());
+    }
+    static_assert(sizeof(CandSum) == sizeof(nhdfit_candidates_sum), "copied out as it is");
+    HIPCHK(c, hipMemcpyAsync(sum_out, dsum, (size_t)P * sizeof *sum_out, hipMemcpyDeviceToHost, c->streams.use(0)));
+    HIPCHK(c, hipMemcpyAsync(out, q.cand_out.p, (size_t)P * K * sizeof *out, hipMemcpyDeviceToHost, c->streams.use(0)));
+    HIPCHK(c, c->streams.wait(0));
+    for (uint32_t p = 0; p < P; ++p) sum_out[p].form = form[p];
+    return NHDFIT_OK;
+}
+
+// The group form: a shard's lists and sums go into the group's by the rule of candidates_merge.h.
+int nhdfit_group_candidates(nhdfit_group* g, const nhdfit_req* reqs, uint32_t P, double now, const uint64_t* const* cand, uint32_t K,
+                            nhdfit_candidates_sum* sum_out, nhdfit_candidate* out, int32_t* owner_out) {
+    if (!g || !reqs || !P || !sum_out || !out || !K || K > NHDFIT_CANDIDATES_MAX_K) return NHDFIT_E_INVAL;
+    std::vector<nhdfit_candidates_sum> part(P);
+    std::vector<nhdfit_candidate> part_list((size_t)P * K);
+    memset(sum_out, 0, (size_t)P * sizeof *sum_out);
+    memset(out, 0, (size_t)P * K * sizeof *out);
+    if (owner_out) std::fill(owner_out, owner_out + (size_t)P * K, -1);
+    return group_each(g, [&](nhdfit_ctx* c, size_t k) {
+        const int rc = nhdfit_candidates(c, reqs, P, now, shard_ptr(cand, k), K, part.data(), part_list.data());
+        if (!rc) merge_candidate_lists(sum_out, out, owner_out, part.data(), part_list.data(), P, K, (int32_t)k);
         return rc;
     });
 }

@@ -225,6 +225,34 @@ class Headroom:
         return f"Headroom({self.summary()!r})"
 
 
+class Candidates:
+    """Where one pod could go, in the order the scheduler would get there (HipMatcher.Candidates): `entries` - `(name, mapping)`
+    tuples exactly as FindNode returns them; entries[0] is FindNode's answer, entries[j] what FindNode answers once the j nodes in
+    front of it are out of `nl`; empty where FindNode answers (None,) - `feasible` (every node of `nl` that FindNode chooses among:
+    the FITS count of ExplainNode), `preferred` (those of them without GPUs, for a pod without GPUs: the scheduler takes them first;
+    0 otherwise) and `k`, the length asked for.  `error`: why the pod itself could not be evaluated - then the list is empty and
+    says nothing about the cluster."""
+
+    def __init__(self, entries: List[Tuple], feasible: int = 0, preferred: int = 0, k: int = 0, nodes: int = 0, form: int = 0,
+                 error: Optional[str] = None):
+        self.entries = entries
+        self.feasible, self.preferred, self.k, self.nodes, self.form = int(feasible), int(preferred), int(k), int(nodes), int(form)
+        self.error = error
+
+    def summary(self) -> str:
+        """"first 8 of 412 feasible nodes (of 65 536; 17 without GPUs come first): node-3, node-9, ..."."""
+        if self.error is not None:
+            return f"the pod was not evaluated against the {_spaced(self.nodes)} nodes: {self.error}."
+        if not self.entries:
+            return f"no feasible node among {_spaced(self.nodes)}."
+        pref = f"; {_spaced(self.preferred)} without GPUs come first" if self.preferred else ""
+        return (f"first {len(self.entries)} of {_spaced(self.feasible)} feasible nodes (of {_spaced(self.nodes)}{pref}): "
+                + ", ".join(e[0] for e in self.entries))
+
+    def __repr__(self) -> str:
+        return f"Candidates({self.summary()!r})"
+
+
 def check_interpreter_set_model() -> None:
     import itertools
     for k, want in _SET_ORDER_PROBES.items():
@@ -954,6 +982,111 @@ class HipMatcher:
                                 flags=None if e is None else (e & np.uint16(pack.HEADROOM_STOPPED | pack.HEADROOM_NOT_EVALUATED)),
                                 limits=lim, limit_stages=stages[k][order] if limits and per_node else None))
         return out
+
+    def Candidates(self, nl: Dict[str, object], top, k: int = 8, pod_groups: Optional[Sequence[str]] = None, now: Optional[float] = None,
+                   strict: Optional[bool] = None) -> Candidates:
+        """CandidatesMany for one pod."""
+        return self.CandidatesMany(nl, [top], k=k, pod_groups=None if pod_groups is None else [pod_groups], now=now, strict=strict)[0]
+
+    def CandidatesMany(self, nl: Dict[str, object], tops: Sequence[object], k: int = 8, pod_groups: Optional[Sequence[Sequence[str]]] = None,
+                       now: Optional[float] = None, strict: Optional[bool] = None) -> List[Candidates]:
+        """Where else each pod of `tops` could go: per pod the first `k` (1..64) nodes of `nl` in the order the scheduler would get to
+        them, each with the mapping FindNode gives for it, picked and mapped on the device in one call (nhdfit_candidates).
+        entries[0] is FindNode's answer; entries[j] is what Matcher().FindNode answers on `nl` without the j nodes in front of it
+        (nhd/Matcher.py:393-421: index order; for a pod without GPUs the nodes without GPUs first) - what a scheduler tries next
+        when a bind fails (nhd/NHDScheduler.py:291-345), and the feasible set a caller's own policy chooses from.  The mirror state
+        is the one FindNodes(nl, tops, pod_groups, now) answers from; nothing about it changes.
+        Pods of the general path (5..8 processing groups, hugepages beyond the pod tile), mirrors with wide nodes and ENABLE_SHARING
+        are composed from FindNodes with the earlier answers left out of `nl`, and ExplainNodes' FITS count: the same answer, slower.
+        A pod no request record can express, or a device error, comes back with `error` set and an empty list - `strict=True`
+        (default: the matcher's) raises instead."""
+        strict = self.strict if strict is None else strict
+        k = int(k)
+        if not 1 <= k <= pack.CANDIDATES_MAX_K:
+            raise ValueError(f"k is {k} (1 .. {pack.CANDIDATES_MAX_K})")
+        n_pods = len(tops)
+        if n_pods == 0:
+            return []
+        if len(nl) == 0:
+            return [Candidates([], k=k) for _ in range(n_pods)]
+        errors: Dict[int, str] = {}
+        for p, top in enumerate(tops):
+            if len(top.proc_groups) == 0:
+                errors[p] = "it has no processing groups (the reference fails on such a pod, Matcher.py:346)"
+        if errors and strict:
+            raise pack.UnsupportedNode(f"candidates: pod {min(errors)} of the call: {errors[min(errors)]}")
+        now = self.clock() if now is None else now
+        cand = self._sync_mirror(nl)
+        out: Dict[int, Candidates] = {}
+        whole = self.packer.sharing or bool(self._table.wide)     # mirrors the device entry does not list: every pod is composed
+        idx = [p for p in range(n_pods) if p not in errors and not whole and not pack.needs_general_path(tops[p])]
+        if idx:
+            beyond: List[Tuple[int, str]] = []
+            reqs = self.packer.digest_many([tops[p] for p in idx], None if pod_groups is None else [pod_groups[p] for p in idx], unsupported=beyond)
+            for j, why in beyond:
+                if strict:
+                    raise pack.UnsupportedNode(f"candidates: pod {idx[j]} of the call: {why}")
+                errors[idx[j]] = f"it cannot be expressed as a request record ({why})"
+            try:
+                sums, entries = self.engine.candidates(reqs, now, k, cand=cand)
+            except NhdFitError as e:
+                if strict:
+                    raise
+                sums = None
+                for p in idx:
+                    errors.setdefault(p, f"the device could not evaluate it ({e})")
+            base = self.engine.global_base
+            for j, p in enumerate(idx):
+                if p in errors:
+                    continue
+                G = int(reqs[j]["n_groups"])
+                got = int(sums[j]["returned"])
+                rows = pack.unpack_mappings(np.ascontiguousarray(entries[j]["map"][:got]))
+                listed = []
+                for e, (gpu, cpu, nic_numa, nic_idx, valid) in zip(entries[j]["score"][:got].tolist(), rows):
+                    name = self._names[winner_index(e) - base]
+                    if not valid:
+                        raise RuntimeError(f"internal error: no mapping produced for feasible node {name}")
+                    listed.append((name, {"gpu": gpu[:G], "cpu": cpu[:G + 1], "nic": list(zip(nic_numa[:G], nic_idx[:G]))}))
+                out[p] = Candidates(listed, feasible=sums[j]["feasible"], preferred=sums[j]["preferred"], k=k, nodes=len(nl), form=sums[j]["form"])
+        for p in range(n_pods):                            # the rest is composed (behind the device call: it matches subsets of `nl`)
+            if p in errors or p in out:
+                continue
+            try:
+                out[p] = self._candidates_composed(nl, tops[p], k, None if pod_groups is None else pod_groups[p], now)
+            except (NhdFitError, pack.UnsupportedNode) as e:
+                if strict:
+                    raise
+                if isinstance(e, NhdFitError):
+                    self._mirror_foreign = True            # whatever the mirror holds now, rebuild it before the next call
+                    self._last_subset = None
+                errors[p] = f"the device could not evaluate it ({e})"
+        for p in sorted(errors):
+            self.logger.error("candidates: pod %d of the call is not evaluated: %s", p, errors[p])
+            out[p] = Candidates([], k=k, nodes=len(nl), error=errors[p])
+        return [out[p] for p in range(n_pods)]
+
+    def _candidates_composed(self, nl, top, k, groups, now) -> Candidates:
+        """Candidates from the existing methods, as ScheduleOne composes: FindNodes again and again on `nl` without the earlier
+        answers (the definition itself), the counts from ExplainNodes' stages."""
+        ex = self.ExplainNodes(nl, [top], None if groups is None else [groups], now=now, per_node=True)[0]
+        if ex.error is not None:
+            raise pack.UnsupportedNode(ex.error)
+        fits = ex.stages == STAGES.index("FITS")
+        preferred = 0
+        if not any(len(g.group_gpus) > 0 for g in top.proc_groups):
+            preferred = sum(1 for nm, ok in zip(nl, fits) if ok and len(nl[nm].gpus) == 0)
+        listed: List[Tuple] = []
+        rest = nl
+        while len(listed) < k:
+            r = self._run_checked(rest, [top], None if groups is None else [groups], now, sequential=False)[0]
+            if r[0] is None:
+                break
+            listed.append(r)
+            rest = {nm: nd for nm, nd in rest.items() if nm != r[0]}
+            if not rest:
+                break
+        return Candidates(listed, feasible=int(fits.sum()), preferred=preferred, k=k, nodes=len(nl))
 
     @property
     def unmirrored(self) -> Dict[str, str]:

@@ -97,6 +97,12 @@ HEADROOM_SUM = np.dtype([("replicas", "<u8"), ("nodes_with_room", "<u4"), ("max_
 HEADROOM_COUNT_MASK, HEADROOM_STOPPED, HEADROOM_NOT_EVALUATED = 0x3FFF, 0x4000, 0x8000
 HEADROOM_FORM_WAVE, HEADROOM_FORM_GENERIC = 1, 2
 HEADROOM_FORM_WIDE = 4           # OR-ed into `form`: the launch over the wide records ran (nhdfit_headroom_general)
+# nhdfit_candidate / nhdfit_candidates_sum (include/nhdfit.h: the first K nodes FindNode would pick)
+CANDIDATE = np.dtype([("score", "<u8"), ("map", MAPPING), ("reserved", "<u4")])
+CANDIDATES_SUM = np.dtype([("feasible", "<u4"), ("preferred", "<u4"), ("returned", "<u4"), ("not_evaluated", "<u4"), ("form", "<u4"),
+                           ("reserved", "<u4", (3,))])
+CANDIDATES_MAX_K = 64
+CANDIDATES_FORM_WAVE, CANDIDATES_FORM_GENERIC = 1, 2
 LIMIT_NONE = 255                 # NHDFIT_LIMIT_NONE: per-node code of nhdfit_headroom_limits where the entry is flagged (no stage)
 # nodes beyond the fast layout: one self-contained record each (include/nhdfit.h nhdfit_wide_node)
 WIDE_MAX_NUMA, WIDE_CORE_WORDS, WIDE_MAX_CORES_PER_NUMA = 4, 8, 128
