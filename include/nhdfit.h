@@ -705,6 +705,29 @@ int nhdfit_candidates(nhdfit_ctx* ctx, const nhdfit_req* reqs, uint32_t P, doubl
 int nhdfit_group_candidates(nhdfit_group* g, const nhdfit_req* reqs, uint32_t P, double now, const uint64_t* const* cand, uint32_t K,
                             nhdfit_candidates_sum* sum_out, nhdfit_candidate* out, int32_t* owner_out);
 
+/* ---- candidates on the general path: wide records and ENABLE_SHARING mirrors, opt-in -----------------------------------
+ * nhdfit_candidates with EVERY mirrored candidate in the list, the ones held as wide records included (3-4 sockets, 65..128 cores per
+ * socket, every node of an ENABLE_SHARING mirror): records, arguments, K range and error codes are nhdfit_candidates'.  The list ranks
+ * them all by descending score word, score_of(pref, global_base + index).  For a wide record `pref` is: the pod requests no GPU
+ * and the record's node has none; "feasible" is the verdict nhdfit_find reaches for it (the general path's enumeration over
+ * itertools.product(range(numa_nodes), ...), nhd/Matcher.py:118, :203, :242, with IsBusy against the busy window at `now`, under
+ * ENABLE_SHARING priced at speed * 0.9 - speed_used, nhd/Node.py:289-291), `cand` applied; its mapping is the one nhdfit_find
+ * gives for that node when it wins (the general CPython set model).  feasible and preferred include the wide records, the wide
+ * candidates evaluated leave not_evaluated - it ends at 0 -, returned is min(K, feasible), and `form` carries
+ * NHDFIT_CANDIDATES_FORM_WIDE.  candidates[0] is nhdfit_find's answer on any mirror; candidates[j] is Matcher().FindNode on `nl`
+ * without the j nodes before it.  On a mirror without wide records the call IS nhdfit_candidates: same launches, same bytes out, no
+ * new bit.  Nothing is written: not the mirror, the wide records, the share records, busy times, staged batch or nhdfit_get_stats.
+ * Not covered: nhdfit_big_req pods (5..8 groups, hugepages beyond the pod tile: no entry here), nodes neither layout holds.
+ * NHDFIT_E_LIMIT: nhdfit_candidates' cases - they hold on a pure ENABLE_SHARING mirror as well, whose planes are placeholders: the
+ * planes' launch runs first on every mirror - and a set of the general set model that outgrew its table (never expected; as
+ * nhdfit_headroom_general reports it): sum_out and out are then all zero. */
+#define NHDFIT_CANDIDATES_FORM_WIDE    4u       /* OR-ed into `form`: the launch over the wide records ran                            */
+int nhdfit_candidates_general(nhdfit_ctx* ctx, const nhdfit_req* reqs, uint32_t P, double now, const uint64_t* cand, uint32_t K,
+                              nhdfit_candidates_sum* sum_out, nhdfit_candidate* out);
+/* ... over every shard of a group, as nhdfit_group_candidates (`form`: the planes' value as there, the wide bit if any shard ran it). */
+int nhdfit_group_candidates_general(nhdfit_group* g, const nhdfit_req* reqs, uint32_t P, double now, const uint64_t* const* cand, uint32_t K,
+                                    nhdfit_candidates_sum* sum_out, nhdfit_candidate* out, int32_t* owner_out);
+
 /* ---- request digest straight from the wire format (host code, no GPU needed) -------------------------
  * The pod's Triad libconfig text -> nhdfit_req, replacing TriadCfgParser(text, False).CfgToTopology(False)
  * (nhd/TriadCfgParser.py:337-380, called from nhd/NHDScheduler.py:262-270) followed by the getters FindNode

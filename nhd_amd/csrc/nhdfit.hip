@@ -70,6 +70,7 @@ namespace {
 #include "candidates_kernel.h"
 #include "limit_kernel.h"
 #include "wide_room_kernel.h"
+#include "wide_candidates_kernel.h"
 
 // ------------------------------------------------------------------------------------------------
 // host side
@@ -157,7 +158,7 @@ struct Pipe {                            // one software pipeline of steps: its 
 };
 
 // Buffers of the query entries - nhdfit_explain / _big (explain_kernel.h), nhdfit_headroom (headroom_kernel.h), _limits
-// (limit_kernel.h), _general (wide_room_kernel.h), nhdfit_candidates (candidates_kernel.h).  One set for all of them: a query waits for its own results before it returns.
+// (limit_kernel.h), _general (wide_room_kernel.h), nhdfit_candidates (candidates_kernel.h), _general (wide_candidates_kernel.h).  One set for all of them: a query waits for its own results before it returns.
 struct QueryBufs {
     DevBuf<nhdfit_req> reqs; DevBuf<nhdfit_big_req> big_reqs;   // the call's requests, by record type
     DevBuf<uint64_t> cand;                                       // [chunks] the call's candidate mask
@@ -169,6 +170,8 @@ struct QueryBufs {
     DevBuf<uint32_t> wide_tickets;                               // general: the wide launch's ticket counters, and behind them its flag words
     DevBuf<uint32_t> cand_work;                                  // candidates: ticket counters, summary records and the blocks' records (one memset)
     DevBuf<nhdfit_candidate> cand_out;                           // candidates: [P][K] entries
+    DevBuf<uint32_t> cand_wide;                                  // general: the wide scan's records, and behind them the wide launch's flag words
+    DevBuf<nhdfit_candidate> cand_merged;                        // general: [P][K] the planes' lists and the wide records' merged (never in place)
 };
 
 // Buffers of mode B (nhdfit_schedule_batch; seq_kernel.h, seq2_kernel.h): sized for one batch of P pods on n nodes by one reserve.
@@ -3170,9 +3173,13 @@ int nhdfit_group_headroom_limits(nhdfit_group* g, const nhdfit_req* reqs, uint32
 }
 
 // ---- candidates: the first K nodes FindNode would pick, each with its mapping (candidates_kernel.h) ---------------------------------
-int nhdfit_candidates(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, double now, const uint64_t* cand, uint32_t K,
-                      nhdfit_candidates_sum* sum_out, nhdfit_candidate* out) {
-    if (!c) return NHDFIT_E_INVAL;
+}  // extern "C"
+namespace {
+// nhdfit_candidates, and with `general` nhdfit_candidates_general: behind k_cand_list, on the same stream, k_wide_cand_scan over (pod,
+// wide record) and k_wide_cand_map over (entry, pod) - the wide candidates leave not_evaluated and join the list, which then comes
+// out of a buffer of its own; skipped on a mirror without wide records.
+int candidates_run(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, double now, const uint64_t* cand, uint32_t K,
+                   nhdfit_candidates_sum* sum_out, nhdfit_candidate* out, bool general) {
     if (!reqs || !P || !sum_out || !out) return fail(c, NHDFIT_E_INVAL, "candidates: requests, sum_out and out are required");
     if (!K || K > NHDFIT_CANDIDATES_MAX_K) return fail(c, NHDFIT_E_INVAL, "candidates: K is %u (1 .. %u)", K, (unsigned)NHDFIT_CANDIDATES_MAX_K);
     for (uint32_t p = 0; p < P; ++p)
@@ -3228,12 +3235,68 @@ int nhdfit_candidates(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, double 
         if (any_g4) hipLaunchKernelGGL(k_cand_list<true>, dim3(nb, S), dim3(kCandBlock), kCandLds, c->streams.use(0), a);
         HIPCHK(c, hipGetLastError());
     }
+    const bool wide_ran = general && c->n_wide != 0;
+    uint32_t wide_flags[4] = {0, 0, 0, 0};
+    if (wide_ran) {
+        const uint32_t wchunks = (c->n_wide + 63) / 64;
+        // blocks (of one wavefront) per pod of the scan: the chip's slots shared out among the pods of a launch, a chunk per block at the least
+        const uint32_t wb = std::max(1u, std::min(wchunks, (slots + slab - 1) / slab));
+        const size_t wrec_words = ((size_t)P * wb * cand_rec_words(K) + 3) & ~size_t(3);
+        HIPCHK(c, q.cand_wide.reserve(wrec_words + 4));
+        HIPCHK(c, q.cand_merged.reserve((size_t)P * K));
+        HIPCHK(c, hipMemsetAsync(q.cand_wide.p, 0, (wrec_words + 4) * sizeof(uint32_t), c->streams.use(0)));
+        HIPCHK(c, hipMemsetAsync(q.cand_merged.p, 0, (size_t)P * K * sizeof(nhdfit_candidate), c->streams.use(0)));
+        WideCandArgs wa;
+        memset(&wa, 0, sizeof wa);
+        wa.wide = c->wide.p; wa.n_wide = c->n_wide; wa.share = c->sharing ? c->wide_share.p : nullptr;
+        wa.caps = c->caps.p; wa.ncls = c->ncls;
+        wa.busy_from = a.busy_from;
+        wa.cand = a.cand;
+        wa.n = n; wa.wchunks = wchunks; wa.K = K; wa.nb = wb;
+        wa.global_base = c->global_base;
+        wa.flags = q.cand_wide.p + wrec_words;
+        for (uint32_t t0 = 0; t0 < P; t0 += slab) {                      // (the planes' slabs)
+            const uint32_t S = std::min(slab, P - t0);
+            wa.reqs = q.reqs.p + t0; wa.sum = dsum + t0;
+            wa.recs = q.cand_wide.p + (size_t)t0 * wb * cand_rec_words(K);
+            wa.planes = q.cand_out.p + (size_t)t0 * K; wa.out = q.cand_merged.p + (size_t)t0 * K;
+            if (wa.share) hipLaunchKernelGGL(k_wide_cand_scan<true>, dim3(wb, S), dim3(kWideCandBlock), 0, c->streams.use(0), wa);
+            else hipLaunchKernelGGL(k_wide_cand_scan<false>, dim3(wb, S), dim3(kWideCandBlock), 0, c->streams.use(0), wa);
+            HIPCHK(c, hipGetLastError());
+            if (wa.share) hipLaunchKernelGGL(k_wide_cand_map<true>, dim3(K, S), dim3(kWideCandBlock), 0, c->streams.use(0), wa);
+            else hipLaunchKernelGGL(k_wide_cand_map<false>, dim3(K, S), dim3(kWideCandBlock), 0, c->streams.use(0), wa);
+            HIPCHK(c, hipGetLastError());
+        }
+        HIPCHK(c, hipMemcpyAsync(wide_flags, wa.flags, sizeof wide_flags, hipMemcpyDeviceToHost, c->streams.use(0)));
+    }
     static_assert(sizeof(CandSum) == sizeof(nhdfit_candidates_sum), "copied out as it is");
     HIPCHK(c, hipMemcpyAsync(sum_out, dsum, (size_t)P * sizeof *sum_out, hipMemcpyDeviceToHost, c->streams.use(0)));
-    HIPCHK(c, hipMemcpyAsync(out, q.cand_out.p, (size_t)P * K * sizeof *out, hipMemcpyDeviceToHost, c->streams.use(0)));
+    HIPCHK(c, hipMemcpyAsync(out, wide_ran ? q.cand_merged.p : q.cand_out.p, (size_t)P * K * sizeof *out, hipMemcpyDeviceToHost, c->streams.use(0)));
     HIPCHK(c, c->streams.wait(0));
-    for (uint32_t p = 0; p < P; ++p) sum_out[p].form = form[p];
+    if (wide_flags[0]) {                                                 // (never expected) no half-mapped list goes out with the error
+        memset(sum_out, 0, (size_t)P * sizeof *sum_out);
+        memset(out, 0, (size_t)P * K * sizeof *out);
+        return fail(c, NHDFIT_E_LIMIT, "the set model of a wide node's mapping outgrew its table");
+    }
+    for (uint32_t p = 0; p < P; ++p) {
+        sum_out[p].form = form[p] | (wide_ran ? NHDFIT_CANDIDATES_FORM_WIDE : 0u);
+        if (wide_ran) sum_out[p].returned = std::min(K, sum_out[p].feasible);    // (the device's is the planes' count)
+    }
     return NHDFIT_OK;
+}
+}  // namespace
+extern "C" {
+
+int nhdfit_candidates(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, double now, const uint64_t* cand, uint32_t K,
+                      nhdfit_candidates_sum* sum_out, nhdfit_candidate* out) {
+    if (!c) return NHDFIT_E_INVAL;
+    return candidates_run(c, reqs, P, now, cand, K, sum_out, out, /*general=*/false);
+}
+
+int nhdfit_candidates_general(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, double now, const uint64_t* cand, uint32_t K,
+                              nhdfit_candidates_sum* sum_out, nhdfit_candidate* out) {
+    if (!c) return NHDFIT_E_INVAL;
+    return candidates_run(c, reqs, P, now, cand, K, sum_out, out, /*general=*/true);
 }
 
 // The group form: a shard's lists and sums go into the group's by the rule of candidates_merge.h.
@@ -3250,6 +3313,35 @@ int nhdfit_group_candidates(nhdfit_group* g, const nhdfit_req* reqs, uint32_t P,
         if (!rc) merge_candidate_lists(sum_out, out, owner_out, part.data(), part_list.data(), P, K, (int32_t)k);
         return rc;
     });
+}
+
+// (`form`: the planes' value as there, the wide bit if any shard ran it)
+int nhdfit_group_candidates_general(nhdfit_group* g, const nhdfit_req* reqs, uint32_t P, double now, const uint64_t* const* cand, uint32_t K,
+                                    nhdfit_candidates_sum* sum_out, nhdfit_candidate* out, int32_t* owner_out) {
+    if (!g || !reqs || !P || !sum_out || !out || !K || K > NHDFIT_CANDIDATES_MAX_K) return NHDFIT_E_INVAL;
+    std::vector<nhdfit_candidates_sum> part(P);
+    std::vector<nhdfit_candidate> part_list((size_t)P * K);
+    std::vector<uint32_t> wide_bit(P, 0u);
+    memset(sum_out, 0, (size_t)P * sizeof *sum_out);
+    memset(out, 0, (size_t)P * K * sizeof *out);
+    if (owner_out) std::fill(owner_out, owner_out + (size_t)P * K, -1);
+    const int rc = group_each(g, [&](nhdfit_ctx* c, size_t k) {
+        const int rc = nhdfit_candidates_general(c, reqs, P, now, shard_ptr(cand, k), K, part.data(), part_list.data());
+        if (rc) return rc;
+        for (uint32_t p = 0; p < P; ++p) {                               // the merge takes the larger instantiation: the bit rides beside it
+            wide_bit[p] |= part[p].form & NHDFIT_CANDIDATES_FORM_WIDE;
+            part[p].form &= ~NHDFIT_CANDIDATES_FORM_WIDE;
+        }
+        merge_candidate_lists(sum_out, out, owner_out, part.data(), part_list.data(), P, K, (int32_t)k);
+        return rc;
+    });
+    if (!rc) for (uint32_t p = 0; p < P; ++p) sum_out[p].form |= wide_bit[p];
+    else {                                                               // no half-merged answer goes out with the error
+        memset(sum_out, 0, (size_t)P * sizeof *sum_out);
+        memset(out, 0, (size_t)P * K * sizeof *out);
+        if (owner_out) std::fill(owner_out, owner_out + (size_t)P * K, -1);
+    }
+    return rc;
 }
 
 int nhdfit_get_stats(nhdfit_ctx* c, nhdfit_stats* out) {

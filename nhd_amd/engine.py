@@ -367,12 +367,13 @@ class Engine:
             return self._headroom(self.lib.nhdfit_headroom_limits, reqs, cand, max_per_node, per_node, limits=True)
         return self._headroom(self.lib.nhdfit_headroom_limits_slab, reqs, cand, max_per_node, per_node, limits=True, last=(int(_slab_bytes),))
 
-    def candidates(self, reqs: np.ndarray, now: float, k: int, cand: Optional[np.ndarray] = None):
+    def candidates(self, reqs: np.ndarray, now: float, k: int, cand: Optional[np.ndarray] = None, general: bool = False):
         """(sums [P] pack.CANDIDATES_SUM, entries [P][k] pack.CANDIDATE) for ordinary requests (pack.REQ): per pod the first k nodes
         FindNode would pick, in the order it would get there, each with its mapping (nhdfit_candidates); entries past `returned` are
-        all zero.  Candidates held as wide records are counted in `not_evaluated`, not listed."""
+        all zero.  Candidates held as wide records are counted in `not_evaluated`, not listed - with `general`
+        (nhdfit_candidates_general) they are ranked and mapped with the others."""
         k = int(k)
-        return self._query(self.lib.nhdfit_candidates, np.ascontiguousarray(reqs, dtype=pack.REQ), cand,
+        return self._query(self.lib.nhdfit_candidates_general if general else self.lib.nhdfit_candidates, np.ascontiguousarray(reqs, dtype=pack.REQ), cand,
                            [((), pack.CANDIDATES_SUM), ((k,), pack.CANDIDATE)], before=(float(now),), after=(k,))
 
     def big_commit(self, node: int, req: np.ndarray, mapping: np.ndarray, busy_time: float) -> np.ndarray:
@@ -815,18 +816,20 @@ class GroupEngine:
         entries and stages put together in global node order."""
         return self._headroom("headroom_limits", reqs, cand, max_per_node, per_node, limits=True)
 
-    def candidates(self, reqs: np.ndarray, now: float, k: int, cand: Optional[np.ndarray] = None):
+    def candidates(self, reqs: np.ndarray, now: float, k: int, cand: Optional[np.ndarray] = None, general: bool = False):
         """Engine.candidates over every shard: the shards' lists merged per pod by descending score, the sums added
-        (nhdfit_group_candidates; shards of host twins: sharding.merge_candidates, the same rule).  The scores carry global indices."""
+        (nhdfit_group_candidates / _general; shards of host twins: sharding.merge_candidates, the same rule).  The scores carry global
+        indices."""
         from .sharding import merge_candidates
         reqs = np.ascontiguousarray(reqs, dtype=pack.REQ)
         k = int(k)
         if self.group is not None:
             return self._query(reqs, cand, False, [((), pack.CANDIDATES_SUM, None), ((k,), pack.CANDIDATE, None), ((k,), np.int32, None)],
-                               "nhdfit_group_candidates", None, before=(float(now),), after=(k,))[:2]
+                               "nhdfit_group_candidates_general" if general else "nhdfit_group_candidates", None, before=(float(now),), after=(k,))[:2]
         if cand is not None:
             cand = np.ascontiguousarray(cand, dtype=np.uint64)
-        parts = [s.candidates(reqs, now, k, cand=None if cand is None else np.ascontiguousarray(cand[lo // 64:(hi + 63) // 64]))
+        more = {"general": True} if general else {}
+        parts = [s.candidates(reqs, now, k, cand=None if cand is None else np.ascontiguousarray(cand[lo // 64:(hi + 63) // 64]), **more)
                  for s, (lo, hi) in zip(self.shards, self._bounds) if hi > lo]
         if not parts or not len(reqs):
             return np.zeros(len(reqs), pack.CANDIDATES_SUM), np.zeros((len(reqs), k), pack.CANDIDATE)

@@ -984,12 +984,13 @@ class HipMatcher:
         return out
 
     def Candidates(self, nl: Dict[str, object], top, k: int = 8, pod_groups: Optional[Sequence[str]] = None, now: Optional[float] = None,
-                   strict: Optional[bool] = None) -> Candidates:
+                   strict: Optional[bool] = None, general: bool = False) -> Candidates:
         """CandidatesMany for one pod."""
-        return self.CandidatesMany(nl, [top], k=k, pod_groups=None if pod_groups is None else [pod_groups], now=now, strict=strict)[0]
+        return self.CandidatesMany(nl, [top], k=k, pod_groups=None if pod_groups is None else [pod_groups], now=now, strict=strict,
+                                   general=general)[0]
 
     def CandidatesMany(self, nl: Dict[str, object], tops: Sequence[object], k: int = 8, pod_groups: Optional[Sequence[Sequence[str]]] = None,
-                       now: Optional[float] = None, strict: Optional[bool] = None) -> List[Candidates]:
+                       now: Optional[float] = None, strict: Optional[bool] = None, general: bool = False) -> List[Candidates]:
         """Where else each pod of `tops` could go: per pod the first `k` (1..64) nodes of `nl` in the order the scheduler would get to
         them, each with the mapping FindNode gives for it, picked and mapped on the device in one call (nhdfit_candidates).
         entries[0] is FindNode's answer; entries[j] is what Matcher().FindNode answers on `nl` without the j nodes in front of it
@@ -998,6 +999,9 @@ class HipMatcher:
         is the one FindNodes(nl, tops, pod_groups, now) answers from; nothing about it changes.
         Pods of the general path (5..8 processing groups, hugepages beyond the pod tile), mirrors with wide nodes and ENABLE_SHARING
         are composed from FindNodes with the earlier answers left out of `nl`, and ExplainNodes' FITS count: the same answer, slower.
+        general=True (nhdfit_candidates_general): every pod that is not of the general path is answered by the device call on ANY
+        mirror - plain, with wide nodes, ENABLE_SHARING - the wide records ranked and mapped with the others; pods of 5..8 groups are
+        still composed.
         A pod no request record can express, or a device error, comes back with `error` set and an empty list - `strict=True`
         (default: the matcher's) raises instead."""
         strict = self.strict if strict is None else strict
@@ -1018,7 +1022,8 @@ class HipMatcher:
         now = self.clock() if now is None else now
         cand = self._sync_mirror(nl)
         out: Dict[int, Candidates] = {}
-        whole = self.packer.sharing or bool(self._table.wide)     # mirrors the device entry does not list: every pod is composed
+        # mirrors the plain device entry does not list: every pod is composed
+        whole = not general and (self.packer.sharing or bool(self._table.wide))
         idx = [p for p in range(n_pods) if p not in errors and not whole and not pack.needs_general_path(tops[p])]
         if idx:
             beyond: List[Tuple[int, str]] = []
@@ -1028,7 +1033,7 @@ class HipMatcher:
                     raise pack.UnsupportedNode(f"candidates: pod {idx[j]} of the call: {why}")
                 errors[idx[j]] = f"it cannot be expressed as a request record ({why})"
             try:
-                sums, entries = self.engine.candidates(reqs, now, k, cand=cand)
+                sums, entries = self.engine.candidates(reqs, now, k, cand=cand, **({"general": True} if general else {}))
             except NhdFitError as e:
                 if strict:
                     raise

@@ -103,6 +103,7 @@ CANDIDATES_SUM = np.dtype([("feasible", "<u4"), ("preferred", "<u4"), ("returned
                            ("reserved", "<u4", (3,))])
 CANDIDATES_MAX_K = 64
 CANDIDATES_FORM_WAVE, CANDIDATES_FORM_GENERIC = 1, 2
+CANDIDATES_FORM_WIDE = 4         # OR-ed into `form`: the launch over the wide records ran (nhdfit_candidates_general)
 LIMIT_NONE = 255                 # NHDFIT_LIMIT_NONE: per-node code of nhdfit_headroom_limits where the entry is flagged (no stage)
 # nodes beyond the fast layout: one self-contained record each (include/nhdfit.h nhdfit_wide_node)
 WIDE_MAX_NUMA, WIDE_CORE_WORDS, WIDE_MAX_CORES_PER_NUMA = 4, 8, 128
