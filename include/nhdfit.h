@@ -728,6 +728,28 @@ int nhdfit_candidates_general(nhdfit_ctx* ctx, const nhdfit_req* reqs, uint32_t 
 int nhdfit_group_candidates_general(nhdfit_group* g, const nhdfit_req* reqs, uint32_t P, double now, const uint64_t* const* cand, uint32_t K,
                                     nhdfit_candidates_sum* sum_out, nhdfit_candidate* out, int32_t* owner_out);
 
+/* ---- candidates of big requests: pods of 5..8 processing groups, opt-in ---------------------------------------------------
+ * nhdfit_candidates_general's semantics for a nhdfit_big_req, over EVERY mirrored node - the planes' nodes and the wide records, on
+ * plain, mixed and ENABLE_SHARING mirrors alike.  Feasible: nhdfit_big_find's verdict for the pair (the `cand` bit, wide_fits with
+ * the busy flag; it equals nhdfit_explain_big's FITS); preferred: the pod asks for no GPU and the node has none; ranking: descending
+ * score word.  candidates[0] is nhdfit_big_find's score word and mapping bit for bit; candidates[j] is Matcher().FindNode on `nl`
+ * without the j nodes before it, with the mapping nhdfit_big_find gives for that node when it wins.  returned = min(K, feasible),
+ * not_evaluated = 0, form = NHDFIT_CANDIDATES_FORM_BIG; entries past `returned` are all zero.  K: 1..NHDFIT_CANDIDATES_MAX_K
+ * (NHDFIT_E_INVAL otherwise); P <= 65535 (NHDFIT_E_LIMIT); NHDFIT_E_STATE without a dictionary.  A (pod, node) pair that runs out of
+ * NHDFIT_BIG_NIC_BUDGET, or a set table that overflows: NHDFIT_E_LIMIT with sum_out and out all zero.  Nothing is written - not the
+ * mirror, the wide or share records, busy times, the staged batch, nhdfit_get_stats (big_nic_steps_max stays as it was). */
+typedef struct {
+    uint64_t score;                             /* the score word, as nhdfit_big_find reports it                                     */
+    nhdfit_big_mapping map;
+    uint32_t reserved;
+} nhdfit_big_candidate;                         /* 48 bytes */
+#define NHDFIT_CANDIDATES_FORM_BIG     8u       /* `form` of nhdfit_candidates_big                                                    */
+int nhdfit_candidates_big(nhdfit_ctx* ctx, const nhdfit_big_req* reqs, uint32_t P, double now, const uint64_t* cand, uint32_t K,
+                          nhdfit_candidates_sum* sum_out, nhdfit_big_candidate* out);
+/* ... over every shard of a group, as nhdfit_group_candidates. */
+int nhdfit_group_candidates_big(nhdfit_group* g, const nhdfit_big_req* reqs, uint32_t P, double now, const uint64_t* const* cand, uint32_t K,
+                                nhdfit_candidates_sum* sum_out, nhdfit_big_candidate* out, int32_t* owner_out);
+
 /* ---- request digest straight from the wire format (host code, no GPU needed) -------------------------
  * The pod's Triad libconfig text -> nhdfit_req, replacing TriadCfgParser(text, False).CfgToTopology(False)
  * (nhd/TriadCfgParser.py:337-380, called from nhd/NHDScheduler.py:262-270) followed by the getters FindNode

@@ -31,14 +31,16 @@ NHD_HD bool cand_merged_entry(const uint64_t* a, uint32_t na, const uint64_t* b,
 // merged by descending score and cut at K; a score names one node of one shard, so no two entries tie.  Counts add; `returned` is
 // min(K, feasible) of the sum; the instantiation (`form`) takes the larger.  owner (optional, [P][K]): the shard of each entry, -1
 // past `returned`.  The caller starts from all-zero sums and lists (owner: -1).
-inline void merge_candidate_lists(nhdfit_candidates_sum* sum, nhdfit_candidate* list, int32_t* owner, const nhdfit_candidates_sum* part,
-                                  const nhdfit_candidate* part_list, uint32_t P, uint32_t K, int32_t shard) {
-    nhdfit_candidate row[NHDFIT_CANDIDATES_MAX_K];
+// Entry: nhdfit_candidate or nhdfit_big_candidate - only the score words are compared, an entry moves as a whole.
+template <class Entry>
+inline void merge_candidate_lists(nhdfit_candidates_sum* sum, Entry* list, int32_t* owner, const nhdfit_candidates_sum* part,
+                                  const Entry* part_list, uint32_t P, uint32_t K, int32_t shard) {
+    Entry row[NHDFIT_CANDIDATES_MAX_K];
     int32_t own[NHDFIT_CANDIDATES_MAX_K];
     for (uint32_t p = 0; p < P; ++p) {
         nhdfit_candidates_sum& s = sum[p];
-        nhdfit_candidate* a = list + (size_t)p * K;
-        const nhdfit_candidate* b = part_list + (size_t)p * K;
+        Entry* a = list + (size_t)p * K;
+        const Entry* b = part_list + (size_t)p * K;
         int32_t* o = owner ? owner + (size_t)p * K : nullptr;
         const uint32_t na = s.returned, nb = part[p].returned;
         uint32_t i = 0, j = 0, k = 0;

@@ -71,6 +71,7 @@ namespace {
 #include "limit_kernel.h"
 #include "wide_room_kernel.h"
 #include "wide_candidates_kernel.h"
+#include "big_candidates_kernel.h"
 
 // ------------------------------------------------------------------------------------------------
 // host side
@@ -158,7 +159,7 @@ struct Pipe {                            // one software pipeline of steps: its 
 };
 
 // Buffers of the query entries - nhdfit_explain / _big (explain_kernel.h), nhdfit_headroom (headroom_kernel.h), _limits
-// (limit_kernel.h), _general (wide_room_kernel.h), nhdfit_candidates (candidates_kernel.h), _general (wide_candidates_kernel.h).  One set for all of them: a query waits for its own results before it returns.
+// (limit_kernel.h), _general (wide_room_kernel.h), nhdfit_candidates (candidates_kernel.h), _general (wide_candidates_kernel.h), _big (big_candidates_kernel.h).  One set for all of them: a query waits for its own results before it returns.
 struct QueryBufs {
     DevBuf<nhdfit_req> reqs; DevBuf<nhdfit_big_req> big_reqs;   // the call's requests, by record type
     DevBuf<uint64_t> cand;                                       // [chunks] the call's candidate mask
@@ -172,6 +173,9 @@ struct QueryBufs {
     DevBuf<nhdfit_candidate> cand_out;                           // candidates: [P][K] entries
     DevBuf<uint32_t> cand_wide;                                  // general: the wide scan's records, and behind them the wide launch's flag words
     DevBuf<nhdfit_candidate> cand_merged;                        // general: [P][K] the planes' lists and the wide records' merged (never in place)
+    DevBuf<uint32_t> big_cand_work;                              // candidates of big requests: summary records, the blocks' records, lists, counts, flag words (one memset)
+    DevBuf<nhdfit_big_candidate> big_cand_out;                   // ... [P][K] entries
+    DevBuf<int32_t> big_cand_scratch;                            // ... [workers][stride] set tables of the mappings that do not fit LDS
 };
 
 // Buffers of mode B (nhdfit_schedule_batch; seq_kernel.h, seq2_kernel.h): sized for one batch of P pods on n nodes by one reserve.
@@ -3284,6 +3288,100 @@ int candidates_run(nhdfit_ctx* c, const nhdfit_req* reqs, uint32_t P, double now
     }
     return NHDFIT_OK;
 }
+
+// nhdfit_candidates_big: k_big_cand_scan over (block, pod), k_big_cand_pick per pod, k_big_cand_map over the (pod, entry) pairs, on one
+// stream (big_candidates_kernel.h).  The mappings' tables are sized as nhdfit_big_find sizes them.
+int candidates_big_run(nhdfit_ctx* c, const nhdfit_big_req* reqs, uint32_t P, double now, const uint64_t* cand, uint32_t K,
+                       nhdfit_candidates_sum* sum_out, nhdfit_big_candidate* out) {
+    if (!reqs || !P || !sum_out || !out) return fail(c, NHDFIT_E_INVAL, "candidates: requests, sum_out and out are required");
+    if (!K || K > NHDFIT_CANDIDATES_MAX_K) return fail(c, NHDFIT_E_INVAL, "candidates: K is %u (1 .. %u)", K, (unsigned)NHDFIT_CANDIDATES_MAX_K);
+    if (P > 65535u) return fail(c, NHDFIT_E_LIMIT, "%u big requests in one call (<= 65535)", P);
+    memset(sum_out, 0, (size_t)P * sizeof *sum_out);
+    memset(out, 0, (size_t)P * K * sizeof *out);
+    if (c->n && !c->ncls) return fail(c, NHDFIT_E_STATE, "set the dictionary first (nhdfit_set_dictionary: the NIC capacity classes)");
+    const uint32_t n = c->n;
+    if (!n) return NHDFIT_OK;
+    QueryBufs& q = c->q;
+    TRY(stage_query(c, q.big_reqs, reqs, P, cand));
+    const uint32_t chunks = (n + 63) / 64, wchunks = (c->n_wide + 63) / 64;
+    // blocks (of one wavefront) per pod and range: the chip's slots shared out among the pods of the launch, a chunk per block at the least
+    const uint32_t slots = 4u * (uint32_t)c->prop.multiProcessorCount;
+    const uint32_t nbp = std::max(1u, std::min(chunks, (slots + P - 1) / P));
+    const uint32_t nbw = wchunks ? std::max(1u, std::min(wchunks, (slots + P - 1) / P)) : 0u;
+    const size_t sum_words = (size_t)P * (sizeof(CandSum) / 4), rec_words = (size_t)P * (nbp + nbw) * cand_rec_words(K), list_words = (size_t)P * K;
+    const size_t work_words = (sum_words + rec_words + list_words + 4 + 3) & ~size_t(3), item_at = work_words;      // (16-byte aligned)
+    HIPCHK(c, q.big_cand_work.reserve(work_words + 4 * list_words));
+    HIPCHK(c, q.big_cand_out.reserve((size_t)P * K));
+    HIPCHK(c, hipMemsetAsync(q.big_cand_work.p, 0, work_words * sizeof(uint32_t), c->streams.use(0)));
+    HIPCHK(c, hipMemsetAsync(q.big_cand_out.p, 0, (size_t)P * K * sizeof(nhdfit_big_candidate), c->streams.use(0)));
+    // set tables of one mapping, as nhdfit_big_find: the call's largest group count on the mirror's widest node; as many mappings at a time as 1 GiB holds
+    uint32_t gmax = 1;
+    for (uint32_t i = 0; i < P; ++i) gmax = std::max(gmax, std::min<uint32_t>(reqs[i].n_groups, NHDFIT_BIG_MAX_GROUPS));
+    const uint32_t umax = std::max<uint32_t>(NHDFIT_MAX_NUMA, c->n_wide ? c->wide_max_numa : 0);
+    const size_t stride = big_scratch_words(umax, gmax);
+    const bool lds_tables = stride * sizeof(int32_t) <= 96 * 1024;
+    const uint32_t workers = (uint32_t)std::max<size_t>(1, std::min<size_t>(std::min<size_t>((size_t)P * K, 128), ((size_t)1 << 28) / stride));
+    HIPCHK(c, q.big_cand_scratch.reserve(lds_tables ? 1 : (size_t)workers * stride));
+    BigCandArgs a;
+    memset(&a, 0, sizeof a);
+    a.p0 = c->p0.p; a.p1 = c->p1.p; a.p2 = c->p2.p; a.p3 = c->p3.p; a.p4 = c->p4.p; a.det = c->det.p; a.n = n;
+    a.wide = c->wide.p; a.n_wide = c->n_wide; a.share = c->sharing ? c->wide_share.p : nullptr;
+    a.reqs = q.big_reqs.p; a.P = P; a.caps = c->caps.p; a.busy_from = busy_threshold(now);
+    a.cand = cand ? q.cand.p : nullptr;
+    a.chunks = chunks; a.wchunks = wchunks; a.nb_planes = nbp; a.nb_wide = nbw; a.K = K;
+    a.global_base = c->global_base;
+    a.sum = reinterpret_cast<CandSum*>(q.big_cand_work.p);
+    a.recs = q.big_cand_work.p + sum_words;
+    a.list = a.recs + rec_words; a.flags = a.list + list_words;
+    a.items = reinterpret_cast<uint4*>(q.big_cand_work.p + item_at); a.out = q.big_cand_out.p;
+    BigCandMapArgs ma;
+    memset(&ma, 0, sizeof ma);
+    ma.p0 = a.p0; ma.p1 = a.p1; ma.p2 = a.p2; ma.p3 = a.p3; ma.p4 = a.p4; ma.det = a.det;
+    ma.wide = a.wide; ma.share = a.share; ma.reqs = a.reqs; ma.pairs = P * K; ma.caps = a.caps;
+    ma.items = a.items; ma.out = a.out; ma.flags = a.flags;
+    ma.scratch = q.big_cand_scratch.p; ma.stride = stride; ma.workers = workers; ma.lds_tables = lds_tables ? 1u : 0u;
+    ma.slots_g = (int32_t)wide_table_slots(wide_ipow(umax, gmax)); ma.slots_c = (int32_t)wide_table_slots(wide_ipow(umax, gmax + 1));
+    const size_t map_lds = lds_tables ? stride * sizeof(int32_t) : 0;
+    hipStream_t st = c->streams.use(0);
+    // the mappings: the wavefront form's pairs where the tables fit LDS, the one-thread form's where the mirror can have any
+    const bool any_wave = lds_tables, any_one = !lds_tables || umax > NHDFIT_MAX_NUMA;
+    if (a.share) {
+        hipLaunchKernelGGL(k_big_cand_scan<true>, dim3(nbp + nbw, P), dim3(kBigCandBlock), 0, st, a);
+        hipLaunchKernelGGL(k_big_cand_pick<true>, dim3(P), dim3(kBigCandBlock), 0, st, a);
+        if (lds_tables) {
+            HIPCHK(c, hipFuncSetAttribute((const void*)k_big_cand_map<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
+            HIPCHK(c, hipFuncSetAttribute((const void*)k_big_cand_map<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
+        }
+        if (any_wave) hipLaunchKernelGGL((k_big_cand_map<true, true>), dim3(workers), dim3(kBigCandBlock), map_lds, st, ma);
+        if (any_one) hipLaunchKernelGGL((k_big_cand_map<true, false>), dim3(workers), dim3(kBigCandBlock), map_lds, st, ma);
+    } else {
+        hipLaunchKernelGGL(k_big_cand_scan<false>, dim3(nbp + nbw, P), dim3(kBigCandBlock), 0, st, a);
+        hipLaunchKernelGGL(k_big_cand_pick<false>, dim3(P), dim3(kBigCandBlock), 0, st, a);
+        if (lds_tables) {
+            HIPCHK(c, hipFuncSetAttribute((const void*)k_big_cand_map<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
+            HIPCHK(c, hipFuncSetAttribute((const void*)k_big_cand_map<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
+        }
+        if (any_wave) hipLaunchKernelGGL((k_big_cand_map<false, true>), dim3(workers), dim3(kBigCandBlock), map_lds, st, ma);
+        if (any_one) hipLaunchKernelGGL((k_big_cand_map<false, false>), dim3(workers), dim3(kBigCandBlock), map_lds, st, ma);
+    }
+    HIPCHK(c, hipGetLastError());
+    uint32_t fl[4] = {0, 0, 0, 0};
+    HIPCHK(c, hipMemcpyAsync(sum_out, a.sum, (size_t)P * sizeof *sum_out, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(out, ma.out, (size_t)P * K * sizeof *out, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(fl, a.flags, sizeof fl, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, c->streams.wait(0));
+    if (fl[0] || fl[1]) {                                                // no half-answered list goes out with the error
+        memset(sum_out, 0, (size_t)P * sizeof *sum_out);
+        memset(out, 0, (size_t)P * K * sizeof *out);
+        if (fl[1]) return fail(c, NHDFIT_E_LIMIT, "a big request's NIC stage ran out of search budget on some node (%u steps per pod and node)", (unsigned)NHDFIT_BIG_NIC_BUDGET);
+        return fail(c, NHDFIT_E_LIMIT, "the set model of a big request's mapping outgrew its table");
+    }
+    for (uint32_t p = 0; p < P; ++p) {
+        sum_out[p].returned = std::min(K, sum_out[p].feasible);
+        sum_out[p].form = NHDFIT_CANDIDATES_FORM_BIG;
+    }
+    return NHDFIT_OK;
+}
 }  // namespace
 extern "C" {
 
@@ -3337,6 +3435,34 @@ int nhdfit_group_candidates_general(nhdfit_group* g, const nhdfit_req* reqs, uin
     });
     if (!rc) for (uint32_t p = 0; p < P; ++p) sum_out[p].form |= wide_bit[p];
     else {                                                               // no half-merged answer goes out with the error
+        memset(sum_out, 0, (size_t)P * sizeof *sum_out);
+        memset(out, 0, (size_t)P * K * sizeof *out);
+        if (owner_out) std::fill(owner_out, owner_out + (size_t)P * K, -1);
+    }
+    return rc;
+}
+
+int nhdfit_candidates_big(nhdfit_ctx* c, const nhdfit_big_req* reqs, uint32_t P, double now, const uint64_t* cand, uint32_t K,
+                          nhdfit_candidates_sum* sum_out, nhdfit_big_candidate* out) {
+    if (!c) return NHDFIT_E_INVAL;
+    return candidates_big_run(c, reqs, P, now, cand, K, sum_out, out);
+}
+
+// (every shard answers NHDFIT_CANDIDATES_FORM_BIG or, empty, 0: the merge's larger one)
+int nhdfit_group_candidates_big(nhdfit_group* g, const nhdfit_big_req* reqs, uint32_t P, double now, const uint64_t* const* cand, uint32_t K,
+                                nhdfit_candidates_sum* sum_out, nhdfit_big_candidate* out, int32_t* owner_out) {
+    if (!g || !reqs || !P || !sum_out || !out || !K || K > NHDFIT_CANDIDATES_MAX_K) return NHDFIT_E_INVAL;
+    std::vector<nhdfit_candidates_sum> part(P);
+    std::vector<nhdfit_big_candidate> part_list((size_t)P * K);
+    memset(sum_out, 0, (size_t)P * sizeof *sum_out);
+    memset(out, 0, (size_t)P * K * sizeof *out);
+    if (owner_out) std::fill(owner_out, owner_out + (size_t)P * K, -1);
+    const int rc = group_each(g, [&](nhdfit_ctx* c, size_t k) {
+        const int rc = nhdfit_candidates_big(c, reqs, P, now, shard_ptr(cand, k), K, part.data(), part_list.data());
+        if (!rc) merge_candidate_lists(sum_out, out, owner_out, part.data(), part_list.data(), P, K, (int32_t)k);
+        return rc;
+    });
+    if (rc) {                                                            // no half-merged answer goes out with the error
         memset(sum_out, 0, (size_t)P * sizeof *sum_out);
         memset(out, 0, (size_t)P * K * sizeof *out);
         if (owner_out) std::fill(owner_out, owner_out + (size_t)P * K, -1);

@@ -376,6 +376,14 @@ class Engine:
         return self._query(self.lib.nhdfit_candidates_general if general else self.lib.nhdfit_candidates, np.ascontiguousarray(reqs, dtype=pack.REQ), cand,
                            [((), pack.CANDIDATES_SUM), ((k,), pack.CANDIDATE)], before=(float(now),), after=(k,))
 
+    def candidates_big(self, reqs: np.ndarray, now: float, k: int, cand: Optional[np.ndarray] = None):
+        """(sums [P] pack.CANDIDATES_SUM, entries [P][k] pack.BIG_CANDIDATE) for big requests (pack.BIG_REQ): candidates() over every
+        mirrored node - the planes' nodes and the wide records, on any mirror - ranked and mapped in one call (nhdfit_candidates_big);
+        entries[0] is big_find's answer, `not_evaluated` is 0."""
+        k = int(k)
+        return self._query(self.lib.nhdfit_candidates_big, np.ascontiguousarray(reqs, dtype=pack.BIG_REQ), cand,
+                           [((), pack.CANDIDATES_SUM), ((k,), pack.BIG_CANDIDATE)], before=(float(now),), after=(k,))
+
     def big_commit(self, node: int, req: np.ndarray, mapping: np.ndarray, busy_time: float) -> np.ndarray:
         """The commit step of a big request on node `node` (ordinary or wide): updates the mirror, returns pack.BIG_PLACEMENT."""
         out = np.zeros((), pack.BIG_PLACEMENT)
@@ -834,6 +842,23 @@ class GroupEngine:
         if not parts or not len(reqs):
             return np.zeros(len(reqs), pack.CANDIDATES_SUM), np.zeros((len(reqs), k), pack.CANDIDATE)
         return merge_candidates([p[0] for p in parts], [p[1] for p in parts], k)[:2]
+
+    def candidates_big(self, reqs: np.ndarray, now: float, k: int, cand: Optional[np.ndarray] = None):
+        """Engine.candidates_big over every shard, merged as candidates() merges (nhdfit_group_candidates_big; shards of host twins:
+        sharding.merge_candidates with the big entry's record)."""
+        from .sharding import merge_candidates
+        reqs = np.ascontiguousarray(reqs, dtype=pack.BIG_REQ)
+        k = int(k)
+        if self.group is not None:
+            return self._query(reqs, cand, False, [((), pack.CANDIDATES_SUM, None), ((k,), pack.BIG_CANDIDATE, None), ((k,), np.int32, None)],
+                               "nhdfit_group_candidates_big", None, before=(float(now),), after=(k,))[:2]
+        if cand is not None:
+            cand = np.ascontiguousarray(cand, dtype=np.uint64)
+        parts = [s.candidates_big(reqs, now, k, cand=None if cand is None else np.ascontiguousarray(cand[lo // 64:(hi + 63) // 64]))
+                 for s, (lo, hi) in zip(self.shards, self._bounds) if hi > lo]
+        if not parts or not len(reqs):
+            return np.zeros(len(reqs), pack.CANDIDATES_SUM), np.zeros((len(reqs), k), pack.BIG_CANDIDATE)
+        return merge_candidates([p[0] for p in parts], [p[1] for p in parts], k, entry_dtype=pack.BIG_CANDIDATE)[:2]
 
     def big_commit(self, node: int, req, mapping, busy_time):
         k = self._shard_of(node)

@@ -984,13 +984,13 @@ class HipMatcher:
         return out
 
     def Candidates(self, nl: Dict[str, object], top, k: int = 8, pod_groups: Optional[Sequence[str]] = None, now: Optional[float] = None,
-                   strict: Optional[bool] = None, general: bool = False) -> Candidates:
+                   strict: Optional[bool] = None, general: bool = False, big: bool = False) -> Candidates:
         """CandidatesMany for one pod."""
         return self.CandidatesMany(nl, [top], k=k, pod_groups=None if pod_groups is None else [pod_groups], now=now, strict=strict,
-                                   general=general)[0]
+                                   general=general, big=big)[0]
 
     def CandidatesMany(self, nl: Dict[str, object], tops: Sequence[object], k: int = 8, pod_groups: Optional[Sequence[Sequence[str]]] = None,
-                       now: Optional[float] = None, strict: Optional[bool] = None, general: bool = False) -> List[Candidates]:
+                       now: Optional[float] = None, strict: Optional[bool] = None, general: bool = False, big: bool = False) -> List[Candidates]:
         """Where else each pod of `tops` could go: per pod the first `k` (1..64) nodes of `nl` in the order the scheduler would get to
         them, each with the mapping FindNode gives for it, picked and mapped on the device in one call (nhdfit_candidates).
         entries[0] is FindNode's answer; entries[j] is what Matcher().FindNode answers on `nl` without the j nodes in front of it
@@ -1000,8 +1000,11 @@ class HipMatcher:
         Pods of the general path (5..8 processing groups, hugepages beyond the pod tile), mirrors with wide nodes and ENABLE_SHARING
         are composed from FindNodes with the earlier answers left out of `nl`, and ExplainNodes' FITS count: the same answer, slower.
         general=True (nhdfit_candidates_general): every pod that is not of the general path is answered by the device call on ANY
-        mirror - plain, with wide nodes, ENABLE_SHARING - the wide records ranked and mapped with the others; pods of 5..8 groups are
-        still composed.
+        mirror - plain, with wide nodes, ENABLE_SHARING - the wide records ranked and mapped with the others; pods of the general
+        path are still composed unless `big` is given.
+        big=True (nhdfit_candidates_big): every pod of the general path - 5..8 processing groups, hugepages beyond the pod tile - is
+        digested as a big request, and all of them are answered by ONE device call on whatever mirror is attached: every mirrored
+        node, wide records included, ranked and mapped as FindNode would.  The other pods go where `general` sends them.
         A pod no request record can express, or a device error, comes back with `error` set and an empty list - `strict=True`
         (default: the matcher's) raises instead."""
         strict = self.strict if strict is None else strict
@@ -1054,6 +1057,8 @@ class HipMatcher:
                         raise RuntimeError(f"internal error: no mapping produced for feasible node {name}")
                     listed.append((name, {"gpu": gpu[:G], "cpu": cpu[:G + 1], "nic": list(zip(nic_numa[:G], nic_idx[:G]))}))
                 out[p] = Candidates(listed, feasible=sums[j]["feasible"], preferred=sums[j]["preferred"], k=k, nodes=len(nl), form=sums[j]["form"])
+        if big:                                            # the pods of the general path: one device call on any mirror
+            self._candidates_big(tops, pod_groups, k, now, cand, strict, len(nl), errors, out)
         for p in range(n_pods):                            # the rest is composed (behind the device call: it matches subsets of `nl`)
             if p in errors or p in out:
                 continue
@@ -1070,6 +1075,44 @@ class HipMatcher:
             self.logger.error("candidates: pod %d of the call is not evaluated: %s", p, errors[p])
             out[p] = Candidates([], k=k, nodes=len(nl), error=errors[p])
         return [out[p] for p in range(n_pods)]
+
+    def _candidates_big(self, tops, pod_groups, k, now, cand, strict, n_nodes, errors, out) -> None:
+        """CandidatesMany(big=True) for the pods of the general path: their big request records through ONE engine.candidates_big
+        call; answers into `out`, the pods that cannot be answered into `errors`."""
+        idx, recs = [], []
+        for p, top in enumerate(tops):
+            if p in errors or p in out or not pack.needs_general_path(top):
+                continue
+            try:
+                recs.append(self.packer.digest_big(top, None if pod_groups is None else pod_groups[p]))
+                idx.append(p)
+            except pack.UnsupportedNode as e:              # beyond the big record too (a group of more than 255 cores ...)
+                if strict:
+                    raise pack.UnsupportedNode(f"candidates: pod {p} of the call: {e}") from None
+                errors[p] = f"it cannot be expressed as a request record ({e})"
+        if not idx:
+            return
+        reqs = np.array(recs, dtype=pack.BIG_REQ)
+        try:
+            sums, entries = self.engine.candidates_big(reqs, now, k, cand=cand)
+        except NhdFitError as e:                           # (the call writes nothing: the mirror is what it was)
+            if strict:
+                raise
+            for p in idx:
+                errors[p] = f"the device could not evaluate it ({e})"
+            return
+        base = self.engine.global_base
+        for j, p in enumerate(idx):
+            G = int(reqs[j]["n_groups"])
+            got = int(sums[j]["returned"])
+            rows = pack.unpack_big_mappings(np.ascontiguousarray(entries[j]["map"][:got]))
+            listed = []
+            for e, (gpu, cpu, nic_numa, nic_idx, valid) in zip(entries[j]["score"][:got].tolist(), rows):
+                name = self._names[winner_index(e) - base]
+                if not valid:
+                    raise RuntimeError(f"internal error: no mapping produced for feasible node {name}")
+                listed.append((name, {"gpu": gpu[:G], "cpu": cpu[:G + 1], "nic": list(zip(nic_numa[:G], nic_idx[:G]))}))
+            out[p] = Candidates(listed, feasible=sums[j]["feasible"], preferred=sums[j]["preferred"], k=k, nodes=n_nodes, form=sums[j]["form"])
 
     def _candidates_composed(self, nl, top, k, groups, now) -> Candidates:
         """Candidates from the existing methods, as ScheduleOne composes: FindNodes again and again on `nl` without the earlier

@@ -104,6 +104,7 @@ CANDIDATES_SUM = np.dtype([("feasible", "<u4"), ("preferred", "<u4"), ("returned
 CANDIDATES_MAX_K = 64
 CANDIDATES_FORM_WAVE, CANDIDATES_FORM_GENERIC = 1, 2
 CANDIDATES_FORM_WIDE = 4         # OR-ed into `form`: the launch over the wide records ran (nhdfit_candidates_general)
+CANDIDATES_FORM_BIG = 8          # `form` of nhdfit_candidates_big (pods of 5..8 processing groups: BIG_CANDIDATE below)
 LIMIT_NONE = 255                 # NHDFIT_LIMIT_NONE: per-node code of nhdfit_headroom_limits where the entry is flagged (no stage)
 # nodes beyond the fast layout: one self-contained record each (include/nhdfit.h nhdfit_wide_node)
 WIDE_MAX_NUMA, WIDE_CORE_WORDS, WIDE_MAX_CORES_PER_NUMA = 4, 8, 128
@@ -133,6 +134,9 @@ BIG_PLACEMENT = np.dtype([("proc_take", "<u8", (8, 2)), ("proc_pair", "<u8", (8,
                           ("pad2", "u1", (4,))])
 _BIG_REQ_STRUCT = struct.Struct("<IIiIQ8H8H8HHHHBB8d8d8B8BB31x")
 assert BIG_REQ.itemsize == 256 and _BIG_REQ_STRUCT.size == 256 and BIG_MAPPING.itemsize == 36 and BIG_PLACEMENT.itemsize == 904
+# nhdfit_big_candidate: an entry of nhdfit_candidates_big (CANDIDATE with the big request's mapping)
+BIG_CANDIDATE = np.dtype([("score", "<u8"), ("map", BIG_MAPPING), ("reserved", "<u4")])
+assert BIG_CANDIDATE.itemsize == 48
 CC = np.dtype([("cls", "u1"), ("cnt", "u1")])
 assert (P0.itemsize, P1.itemsize, P2.itemsize, P3.itemsize, P4.itemsize) == (16,) * 5
 _REQ_STRUCT = struct.Struct("<IIiIQ4H4H4HHH4B4d4d4BBBBB")          # REQ, field by field (digest_many packs records with it)

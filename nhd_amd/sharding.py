@@ -36,16 +36,18 @@ def from_ordered_int64(x: np.ndarray) -> np.ndarray:
     return x.view(np.uint64) ^ SIGN
 
 
-def merge_candidates(per_rank_sums, per_rank_entries, k: int):
+def merge_candidates(per_rank_sums, per_rank_entries, k: int, entry_dtype=None):
     """The ranks' answers of Engine.candidates(reqs, now, k) - sums [P] pack.CANDIDATES_SUM and entries [P][k] pack.CANDIDATE per
     rank, each rank over its own shard with its global base - into the cluster's: (sums, entries, owner [P][k] int32, the rank of
     each entry or -1).  The rule of nhdfit_group_candidates (nhd_amd/csrc/candidates_merge.h): per pod the lists are merged by
     descending score - the selection order; a score names one node - and cut at k; counts add, `returned` is min(k, feasible), the
-    instantiation takes the larger.  A pure function: one process per GPU gathers the ranks' answers however it likes."""
+    instantiation takes the larger.  `entry_dtype`: the entries' record, pack.CANDIDATE unless given (pack.BIG_CANDIDATE for the
+    answers of Engine.candidates_big: the rule compares score words only).  A pure function: one process per GPU gathers the ranks'
+    answers however it likes."""
     from . import pack
     P = len(per_rank_sums[0])
     sums = np.zeros(P, pack.CANDIDATES_SUM)
-    entries = np.zeros((P, k), pack.CANDIDATE)
+    entries = np.zeros((P, k), pack.CANDIDATE if entry_dtype is None else entry_dtype)
     owner = np.full((P, k), -1, np.int32)
     for f in ("feasible", "preferred", "not_evaluated"):
         sums[f] = sum(np.asarray(s[f], np.uint32) for s in per_rank_sums)

@@ -15,7 +15,13 @@ of config 2 (4 096 nodes, every node a wide record) and config 4 at 65 536 nodes
 pod at K = 1, 8, 64 and 64 pods at K = 8, each against the composed form at the C-ABI on the same mirror - K successive nhdfit_find
 calls with a shrinking mask, per pod - same protocol, the lists compared first.  `--kernels`: the general calls alone, for a separate
 `rocprofv3 --kernel-trace --stats -- python tools/time_candidates.py --general --kernels` run (k_wide_cand_scan, k_wide_cand_map).
-usage: time_candidates.py [cfg:nodes] [calls per round] [rounds] [--general [--kernels]]"""
+
+`--big`: nhdfit_candidates_big for pods of 5..8 groups (seeded tests/test_big_core.big_spec pods) on config 4 at 65 536 nodes and on
+the 4 096-node ENABLE_SHARING mirror of config 2.  Per mirror, one pod and 64 pods at K = 1, 8, 64, each against the composed form at
+the C-ABI on the same mirror - K successive nhdfit_big_find calls with a shrinking mask, per pod - and one pod's nhdfit_big_find; same
+protocol, the lists compared first.  `--kernels`: the new calls alone, for a separate `rocprofv3 --kernel-trace --stats` run
+(k_big_cand_scan, k_big_cand_pick, k_big_cand_map).
+usage: time_candidates.py [cfg:nodes] [calls per round] [rounds] [--general [--kernels] | --big [--kernels]]"""
 import json
 import os
 import sys
@@ -28,7 +34,7 @@ from nhd_amd import pack  # noqa: E402
 from nhd_amd.engine import Engine, winner_index  # noqa: E402
 from workload import planes, refmodel, synth  # noqa: E402
 
-GENERAL, KERNELS = "--general" in sys.argv, "--kernels" in sys.argv
+GENERAL, KERNELS, BIG = "--general" in sys.argv, "--kernels" in sys.argv, "--big" in sys.argv
 argv = [a for a in sys.argv if not a.startswith("--")]
 cfg, n = (int(x) for x in (argv[1] if len(argv) > 1 else "4:65536").split(":"))
 calls = int(argv[2]) if len(argv) > 2 else 50
@@ -40,8 +46,12 @@ def measure(forms):
     for fn in forms.values():
         for _ in range(3):
             fn()
+    if BIG:                                                    # (calls of milliseconds to seconds: say how far the run is)
+        print(f"warmed up {len(forms)} forms", file=sys.stderr, flush=True)
     medians = {name: [] for name in forms}
-    for _ in range(rounds):
+    for r in range(rounds):
+        if BIG:
+            print(f"round {r + 1} of {rounds}", file=sys.stderr, flush=True)
         ts = {name: [] for name in forms}
         for _ in range(calls):
             for name, fn in forms.items():
@@ -99,6 +109,86 @@ def general_leg(eng, reqs, now):
             rec[case + "_speedup"] = round(base["us_median"] / new["us_median"], 2)
     return rec
 
+
+def big_leg(eng, reqs, now):
+    """One mirror: nhdfit_candidates_big against K successive nhdfit_big_find calls per pod, lists compared first."""
+    chunks = (eng.n + 63) // 64
+    full = np.full(chunks, np.uint64(0xFFFFFFFFFFFFFFFF))
+
+    def composed(pods, k):
+        out = []
+        for p in range(len(pods)):
+            mask, row = full.copy(), []
+            for _ in range(k):
+                score, maps = eng.big_find(pods[p:p + 1], now, cand=mask)
+                if not score[0]:
+                    break
+                i = winner_index(score[0]) - eng.global_base
+                mask[i >> 6] &= ~(np.uint64(1) << np.uint64(i & 63))
+                row.append((int(score[0]), maps[0].tobytes()))
+            out.append(row)
+        return out
+
+    sums, entries = eng.candidates_big(reqs, now, 8, cand=full)
+    first = next(p for p in range(len(reqs)) if sums[p]["feasible"] >= 64)      # the one-pod forms' pod: a list of 64 exists
+    one = reqs[first:first + 1]
+    got = [[(int(e["score"]), e["map"].tobytes()) for e in entries[p][:int(sums[p]["returned"])]] for p in range(len(reqs))]
+    same = got == composed(reqs, 8)
+    assert same, "nhdfit_candidates_big and the composed form disagree"
+    print(f"{eng.n} nodes: lists compared", file=sys.stderr, flush=True)
+    assert (sums["not_evaluated"] == 0).all() and (sums["form"] == pack.CANDIDATES_FORM_BIG).all()
+    rec = {"nodes": eng.n, "wide": eng.n_wide, "pods": len(reqs), "one_pod": first, "one_pod_groups": int(one[0]["n_groups"]),
+           "feasible_one_pod": int(sums[first]["feasible"]), "feasible_64pods": sums["feasible"].tolist(), "listed_64pods_K8": int(sums["returned"].sum()), "lists_equal": bool(same)}
+    forms = {f"big_K{k}": (lambda k=k: eng.candidates_big(one, now, k, cand=full)) for k in (1, 8, 64)}
+    forms.update({f"big_64pods_K{k}": (lambda k=k: eng.candidates_big(reqs, now, k, cand=full)) for k in (1, 8, 64)})
+    if not KERNELS:
+        forms["big_find"] = lambda: eng.big_find(one, now, cand=full)
+        forms.update({f"composed_K{k}": (lambda k=k: composed(one, k)) for k in (1, 8, 64)})
+        forms.update({f"composed_64pods_K{k}": (lambda k=k: composed(reqs, k)) for k in (1, 8, 64)})
+    for name, m in measure(forms).items():
+        rec[name] = spread(m)
+    if not KERNELS:
+        for case in ("K1", "K8", "K64", "64pods_K1", "64pods_K8", "64pods_K64"):
+            new, base = rec["big_" + case], rec["composed_" + case]
+            rec[case + "_faster_beyond_spread"] = bool(new["us_max"] < base["us_min"])
+            rec[case + "_speedup"] = round(base["us_median"] / new["us_median"], 2)
+    return rec
+
+
+if BIG:
+    from nhd_amd.matcher import HipMatcher
+    from oracle import nhd_oracle
+    from tests.test_big_core import big_spec
+    out = {"calls_per_round": calls, "rounds": rounds}
+    rng = np.random.default_rng(18)
+    specs = [big_spec(rng) for _ in range(64)]
+    # config 4 at 65 536 nodes
+    spec = synth.make_cluster(4, n_nodes=65536)
+    pk = pack.Packer()
+    table = planes.planes_from_spec(pk, spec)
+    reqs = np.array([pk.digest_big(refmodel.make_topology(s)) for s in specs], dtype=pack.BIG_REQ)
+    pk.close_signatures()
+    eng = Engine(0)
+    eng.set_dictionary(pk)
+    eng.upload(table)
+    out["c4_65536"] = big_leg(eng, reqs, spec.clock_now)
+    eng.close()
+    # an ENABLE_SHARING mirror of config 2: every node a wide record with its share record
+    spec = synth.make_cluster(2, n_nodes=4096)
+    refmodel.ENABLE_SHARING = nhd_oracle.ENABLE_SHARING = True
+    try:
+        nl = spec.build_nodes()
+        m = HipMatcher(device=0, clock=lambda: spec.clock_now)
+        tops = [refmodel.make_topology(s) for s in specs]
+        c = m.Candidates(nl, tops[0], k=8, big=True)
+        assert c.error is None and m.packer.sharing and len(m.wide_nodes) == len(nl)
+        reqs = np.array([m.packer.digest_big(t) for t in tops], dtype=pack.BIG_REQ)
+        out["c2_sharing"] = big_leg(m.engine, reqs, spec.clock_now)
+        m.engine.close()
+    finally:
+        refmodel.ENABLE_SHARING = nhd_oracle.ENABLE_SHARING = False
+    print(json.dumps(out))
+    sys.exit(0)
 
 if GENERAL:
     from nhd_amd.matcher import HipMatcher
